@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - frames/sec/step of the speech-transformer training step on N MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,13 +12,16 @@ One step = zero_grad + forward + CE(ignore_index=0) + backward + [RCCL gradient
 average] + global-norm clip + Noam-Adam, i.e. train.py:37-46 / train_multi.py:58-68.
 bf16 activations / fp32 accumulate, fp32 master weights.  The headline number is the
 dropout-free step (eval-mode modules under autograd = the parity mode the oracle, the
-goldens and the CPU baseline are quoted in); the same step in training mode
-(model.train(): in-kernel dropout, p = 0.1 / front-end 0.5) is timed in a second pass
-and reported as ``train_mode`` on the same line.
+goldens and the CPU baseline are quoted in), with Adam's update run at a rate of zero so
+that every timed step computes from the same weights and batch (see main()).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying
-``roofline`` (dominant kernel, live HIP-event timing) and ``cpu_baseline`` (the CPU
-oracle restatement timed on this box's host cores; N = 1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up,
+warms up, times --steps steps, writes their outputs (--dump-outputs) and prints the
+headline.  --full then adds everything else: the synced-median and eager timings, the
+exposed all-reduce time, ``roofline`` (dominant kernel, live HIP-event timing), the same
+step in training mode (model.train(): in-kernel dropout, p = 0.1 / front-end 0.5) as
+``train_mode``, decode, loader, shard and CTC blocks, the other scaling partition and
+``cpu_baseline`` (the CPU oracle restatement timed on this box's host cores; N = 1 only).
 """
 import argparse
 import glob
@@ -223,6 +226,52 @@ def cpu_worker(args):
     print(json.dumps(out))
 
 
+def dump_outputs(out_dir, loss, gnorm):
+    """--dump-outputs: what the last timed step returns to its caller (TrainStep: the loss and the global gradient norm the
+    clip used), as float32 ``loss.npy`` and ``grad_norm.npy`` in ``out_dir``."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("loss", loss), ("grad_norm", gnorm)):
+        np.save(os.path.join(out_dir, name + ".npy"), torch.as_tensor(t).detach().float().cpu().reshape(1).numpy())
+
+
+def headline(args, world, frames, elapsed, ms_step, in_len, tgt_len, loss, gnorm, dp_mode):
+    """The result line of every run: the rate of the timed steps and what they computed (--full adds its blocks to it)."""
+    flops = step_flops(in_len, tgt_len, CFG)
+    return {
+        "metric": "frames/sec/step (80-d fbank, 6+6L d256) at 1/2/4/8 MI355X vs CPU ref" if args.config == 2 else
+                  "frames/sec/step (80-d fbank, 12+6L d512 h8: BASELINE config 3) at 1/2/4/8 MI355X vs CPU ref",
+        "value": round(frames * args.steps / elapsed, 1), "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "dp_mode": dp_mode,
+        "higher_is_better": True, "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": "BASELINE config %s, 80-d fbank, %s, "
+                               "T<=1000 (%d valid frames on rank 0), L<=50; fwd+CE+bwd+clip+Adam (rate 0: weights held), dropout off"
+                               % ("2: 6+6L d256 h4 dff1024 V4337" if args.config == 2 else "3: 12+6L d512 h8 dff1024 V4337", ("global B=%d split %d per GPU (strong scaling, SURVEY 8e)" % (args.global_batch, args.global_batch // world))
+                                  if args.global_batch else "B=32 per GPU (weak scaling, train_multi.py:136-139)", int(in_len.sum())),
+                   "global_batch": args.global_batch or BATCH * world, "parallelism": "dp%d" % world,
+                   "launch": "eager" if args.no_graph else "hipGraph replay of the whole step",
+                   "wire": "bf16" if args.wire_bf16 else "fp32", "dp_bucket_mb": args.bucket_mb,
+                   "nccl_algo": os.environ.get("NCCL_ALGO", "default"), "nccl_proto": os.environ.get("NCCL_PROTO", "default")},
+        "loss": round(loss.item(), 4), "grad_norm": round(gnorm.item(), 4),
+        "step_tflops_valid": round(flops / (ms_step * 1e-3) / 1e12, 2),
+        "step_frac_of_bf16_peak": round(flops / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
+    }
+
+
+def finish(out):
+    """Close the process group; rank 0 (``out`` not None) prints the result line as the last line of stdout."""
+    if dist.is_initialized():
+        if dist.get_world_size() > 1:
+            dist.barrier()
+        dist.destroy_process_group()
+    if out is not None:
+        # RCCL prints a version banner through C stdio, which a pipe would otherwise deliver at exit - AFTER this line
+        import ctypes
+        sys.stdout.flush()
+        ctypes.CDLL(None).fflush(None)
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -261,7 +310,16 @@ def main():
                     "kernel's HBM traffic from THEM (roofline.traffic_source = measured) instead of the committed summary")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from Python instead of replaying "
                                                             "the captured HIP graph of the step")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every other measurement of this file "
+                    "(synced / eager timings, exposed all-reduce, roofline, training mode, decode, loader, shard, CTC, the other "
+                    "scaling partition, CPU baseline; the --no-* switches drop single ones); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR", help="write what the last timed step returned "
+                    "(loss, grad_norm) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.pmc or args.dump_kernels:
+        args.full = True          # both feed the roofline pass of the full run
     global CFG
     CFG = {2: C2, 3: C3}[args.config]
     if args.config != 2:          # the extras below are config 2's; config 3 reports its own 4-utterance shard instead
@@ -303,6 +361,12 @@ def main():
     reducer = dp.GradReducer(arena, bucket_bytes=args.bucket_mb << 20, wire_dtype=torch.bfloat16 if args.wire_bf16 else None,
                              force=args.force_dp) if (world > 1 or args.force_dp) else None
     optim = ScheduledOptim(model, CFG["d_model"], U.AttrDict(n_warmup_steps=12000))
+    # The warm-up and timed steps run Noam-Adam's whole update (the same kernels and traffic) at a rate of zero, so that every
+    # timed step computes from the same weights and batch.  The parameter-gradient reductions accumulate with fp32 atomics; on
+    # a moving trajectory Adam turns their last-bit differences on near-zero gradients into +-lr steps, and bf16 rounding
+    # spreads those until, after 25 steps, two runs of the same inputs differ at bf16 noise level - as would two builds.
+    noam = optim.update_learning_rate
+    optim.update_learning_rate = lambda global_step: optim.lr_tensor.fill_(0.0)
     step = TrainStep(model, optim, CFG["vocab_size"], max_grad_norm=5.0, reducer=reducer, use_graph=not args.no_graph)
 
     def shard(global_batch):
@@ -352,6 +416,13 @@ def main():
         if dist.is_initialized():
             dist.destroy_process_group()
         return
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, gnorm)
+    if not args.full:
+        finish(headline(args, world, frames, elapsed, ms_step, in_len, tgt_len, loss, gnorm, getattr(step, "dp_mode", None))
+               if rank == 0 else None)
+        return
+    optim.update_learning_rate = noam             # the extra passes below train on the Noam schedule
 
     # ---- SURVEY 8d's protocol next to the contract's back-to-back mean: a device sync at both edges of EVERY step,
     # median of the per-step wall times; then the same with use_graph off (every kernel launched from Python: what a
@@ -691,34 +762,19 @@ def main():
     out = None
     if rank == 0:
         flops = step_flops(in_len, tgt_len, CFG)
-        out = {
-            "metric": "frames/sec/step (80-d fbank, 6+6L d256) at 1/2/4/8 MI355X vs CPU ref" if args.config == 2 else
-                      "frames/sec/step (80-d fbank, 12+6L d512 h8: BASELINE config 3) at 1/2/4/8 MI355X vs CPU ref",
-            "value": round(frames * args.steps / elapsed, 1), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
+        out = headline(args, world, frames, elapsed, ms_step, in_len, tgt_len, loss, gnorm, getattr(step, "dp_mode", None))
+        out["config"].update(sustained_mfma_clock_mhz=roofline.get("sustained_mfma_clock_mhz"), nominal_clock_mhz=NOMINAL_CLOCK_MHZ,
+                             **box_identity())
+        out.update({
             "ms_per_step_median_synced": round(ms_median, 3),
             "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 3),
             "eager_ms_per_step_synced": None if eager_ms_synced is None else round(eager_ms_synced, 3),
-            "allreduce_exposed_ms": exposed_ms, "dp_mode": getattr(step, "dp_mode", None),
-            "higher_is_better": True, "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": "BASELINE config %s, 80-d fbank, %s, "
-                                   "T<=1000 (%d valid frames on rank 0), L<=50; fwd+CE+bwd+clip+Adam, dropout off"
-                                   % ("2: 6+6L d256 h4 dff1024 V4337" if args.config == 2 else "3: 12+6L d512 h8 dff1024 V4337", ("global B=%d split %d per GPU (strong scaling, SURVEY 8e)" % (args.global_batch, args.global_batch // world))
-                                      if args.global_batch else "B=32 per GPU (weak scaling, train_multi.py:136-139)", int(in_len.sum())),
-                       "global_batch": args.global_batch or BATCH * world, "parallelism": "dp%d" % world,
-                       "launch": "eager" if args.no_graph else "hipGraph replay of the whole step",
-                       "wire": "bf16" if args.wire_bf16 else "fp32", "dp_bucket_mb": args.bucket_mb,
-                       "nccl_algo": os.environ.get("NCCL_ALGO", "default"), "nccl_proto": os.environ.get("NCCL_PROTO", "default"),
-                       "sustained_mfma_clock_mhz": roofline.get("sustained_mfma_clock_mhz"), "nominal_clock_mhz": NOMINAL_CLOCK_MHZ,
-                       **box_identity()},
-            "loss": round(loss.item(), 4), "grad_norm": round(gnorm.item(), 4),
-            "step_tflops_valid": round(flops / (ms_step * 1e-3) / 1e12, 2),
-            "step_frac_of_bf16_peak": round(flops / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
+            "allreduce_exposed_ms": exposed_ms,
             "step_frac_of_bf16_peak_at_sustained_clock": round(flops / (ms_step * 1e-3) / 1e12 / roofline["peak_at_sustained_clock"], 4),
             "kernel_ms_per_step": round(total_ms / 2, 3),
             "roofline": roofline, "kernels": kernels,
             "hbm_bytes_source": "per launch: the launch's own operands, each counted once (st_amd.native._tag io lists)",
-        }
+        })
         if dp_probe is not None:
             out["dp_probe"] = dp_probe
             if out["dp_mode"] is None:
@@ -751,16 +807,7 @@ def main():
         except Exception as e:  # noqa: BLE001 - the GPU number must still be reported
             out["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": None, "kind": "port",
                                    "sample": "CPU baseline did not finish within %ds (%s)" % (args.cpu_timeout, type(e).__name__)}
-    if dist.is_initialized():
-        if world > 1:
-            dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        # RCCL prints a version banner through C stdio, which a pipe would otherwise deliver at exit - AFTER this line
-        import ctypes
-        sys.stdout.flush()
-        ctypes.CDLL(None).fflush(None)
-        print(json.dumps(out), flush=True)        # the last line of stdout
+    finish(out)
 
 
 if __name__ == "__main__":

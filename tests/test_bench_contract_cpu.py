@@ -1,5 +1,5 @@
 """The bench.py output contract, checked on the committed round artefact (profiles/*_bench.json is the JSON line a
-real `python bench.py` run printed on the MI355X): every field the driver reads is present and well-formed."""
+real `python bench.py --full` run printed on the MI355X): every field the driver reads is present and well-formed."""
 import glob
 import json
 import os
@@ -72,3 +72,21 @@ def test_strong_scaling_shards_partition_the_global_batch():
         parts = [bench.shard_batch(full, r, world, 32) for r in range(world)]
         assert all(p[0].shape[0] == 32 // world for p in parts)
         assert torch.equal(torch.cat([p[1] for p in parts]), full[1]) and torch.equal(torch.cat([p[0] for p in parts]), full[0])
+
+
+def test_dump_outputs_writes_what_the_step_returns(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): the step's returned loss and gradient norm - device or host scalars - as
+    float32 loss.npy / grad_norm.npy of shape (1,), and nothing else."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), torch.tensor(2.5), torch.tensor(0.75, dtype=torch.float64))
+    assert sorted(os.listdir(str(out))) == ["grad_norm.npy", "loss.npy"]
+    got = {n: np.load(str(out / (n + ".npy"))) for n in ("loss", "grad_norm")}
+    assert all(a.dtype == np.float32 and a.shape == (1,) for a in got.values())
+    assert got["loss"].tolist() == [2.5] and got["grad_norm"].tolist() == [0.75]

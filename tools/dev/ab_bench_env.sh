@@ -4,7 +4,7 @@ export TMPDIR=/tmp; cd /root/repo
 VAR=$1; ROUNDS=$2; shift 2
 for r in $(seq 1 $ROUNDS); do
   for V in "$@"; do
-    env $VAR=$V python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-train-mode --no-decode --no-dp-probe $BENCH_FLAGS > /tmp/ab_bench.json 2> /tmp/ab_bench.err
+    env $VAR=$V python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-train-mode --no-decode --no-dp-probe $BENCH_FLAGS > /tmp/ab_bench.json 2> /tmp/ab_bench.err
     python - "$VAR" "$V" <<'PY'
 import json, sys
 try:

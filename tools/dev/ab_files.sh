@@ -5,7 +5,7 @@ ROUNDS=$1; shift
 C=speech-tranformer-pytorch_amd/csrc
 for kv in "$@"; do f=${kv%%=*}; cp $C/$f /tmp/_orig_$f; done
 run() { python -c "import __graft_entry__ as g; g.build()" > /tmp/build.log 2>&1 || { echo BUILD FAILED; tail -5 /tmp/build.log; return; }
-  python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-train-mode --no-decode --no-dp-probe $BENCH_FLAGS > /tmp/ab_bench.json 2> /tmp/ab_bench.err
+  python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-train-mode --no-decode --no-dp-probe $BENCH_FLAGS > /tmp/ab_bench.json 2> /tmp/ab_bench.err
   python - "$1" <<'PY'
 import json, sys
 try:
