@@ -33,7 +33,7 @@ typedef void* st_stream_t; /* hipStream_t */
 /* Library ABI version, bumped on any signature change (2: round 5's k_prescaled / dense attention / grad_scale arguments;
  * 3, 4: round 6 - 4 added the column-sum workspace of st_row_chain_bwd).  A host binding must refuse a library whose st_version() differs from the header it was written against:
  * through ctypes / dlsym a stale libst_hip.so would be called with shifted arguments (st_amd/native.py: ABI_VERSION). */
-#define ST_ABI_VERSION 4
+#define ST_ABI_VERSION 5
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -410,6 +410,52 @@ int st_beam_advance(st_stream_t stream, const float* logits, int ldl, int V, int
                     float* scores, long long* tokens, unsigned char* done, long long* lengths, float* hist_scores,
                     long long* back, long long* toks, long long* order, void* work, int* anc, int S, long long* step_next,
                     const float* emb, int emb_rows, const float* pe, int pe_rows, void* x_next, int D);
+
+/* Joint CTC / attention beam search (csrc/st_ctc_decode.hip; Watanabe et al. 2017, Algorithm 2).  x_t(k) = log-softmax of the
+   CTC head's logits of frame t; per hypothesis the CTC state gamma f32 [n][2][T_cap] (row 0 gamma_n, row 1 gamma_b), psi f32 [n]
+   (log prefix probability), last int32 [n] (last token, -1 for the empty prefix), frozen u8 [n] (emitted EOS: later
+   increments are 0).  T_cap is a multiple of 64 and >= every len[b].
+
+   st_ctc_vocab_lp: logits f32 [R][ldl] (packed encoder rows; utterance b owns rows off[b] .. off[b] + len[b] - 1) ->
+   lse[r] = logsumexp(logits[r][:V]) and the vocabulary-major table lpT f32 [B][V][T_cap] = logits - lse (frames t >= len[b]: 0),
+   transposed through LDS tiles. */
+int st_ctc_vocab_lp(st_stream_t stream, const float* logits, int ldl, int R, int V, const int* off, const int* len, int B, int T_cap,
+                    float* lse, float* lpT);
+
+/* The empty prefix in every slot of every utterance (n = B * beam, beam <= 64): gamma_n = -inf, gamma_b[t] = sum_{tau <= t}
+   x_tau(blank) for t < len[b] (-inf beyond), psi = 0, last = -1, frozen = 0. */
+int st_ctc_prefix_init(st_stream_t stream, const float* lpT, int V, int T_cap, const int* len, int B, int beam, int blank, float* gam,
+                       float* psi, int* last, unsigned char* frozen);
+
+/* For every hypothesis i < B * beam and candidate j < K (token cand[i][j], int32): the CTC prefix score of i's prefix
+   extended by it, psi(h) -> cand_psi f32 [n][K], its increment delta[i][j] = psi(h) - psi(i) (-inf when psi(h) = -inf), and
+   the extension's state -> cand_gam f32 [n][K][2][T_cap].  cand == eos: psi(h) = log p_ctc(prefix), no state written;
+   cand == blank (or out of range): -inf.  A frozen hypothesis gets delta 0 and cand_psi = psi(i), no state written.  `done`:
+   NULL or u8 [B] - hypotheses of a done utterance are skipped (nothing written).  T_cap / 64 in {1, 2, 4, 8, 12, 16, 24, 32};
+   K <= 64. */
+int st_ctc_prefix_score(st_stream_t stream, const float* lpT, int V, int T_cap, const int* len, int B, int beam, int blank, int eos,
+                        const int* cand, int K, const float* gam, const float* psi, const int* last, const unsigned char* frozen,
+                        const unsigned char* done, float* cand_gam, float* cand_psi, float* delta);
+
+/* The attention pre-beam: for each of n rows of decoder logits f32 [n][ldl], log-softmax over the first V columns and its K best
+   (best first, lower id on ties) -> ids int32 [n][K], lp f32 [n][K].  V <= 5120, K <= min(64, V). */
+int st_beam_pre_beam(st_stream_t stream, const float* logits, int ldl, int V, int n, int K, int* ids, float* lp);
+
+/* st_beam_advance over beam x K joint candidates: candidate (s, j) = token ids[b * beam + s][j] with score
+   scores[b][s] + (1 - w) lp[.][j] + w delta[.][j] (0 <= w < 1; beam <= 16, beam <= K <= 64), the `beam` best (best first,
+   lower s * K + j on ties); then the same state update, trellis row, order, lineage table (anc, S <= 128), next decoder input
+   (x_next) and step counter (step_next == step, ticket = a zeroed 4-byte device word) as st_beam_advance.  `gam` non-NULL: the
+   CTC state of every new hypothesis of a live utterance is moved from its parent and candidate - psi <- cand_psi, last <- token,
+   gamma <- cand_gam; a frozen parent passes its psi / last / frozen on unchanged; choosing EOS freezes.  T_cap even. */
+int st_beam_advance_joint(st_stream_t stream, const int* ids, const float* lp, const float* delta, int K, float ctc_weight, int beam,
+                          int B, const long long* step, int eos, float* scores, long long* tokens, unsigned char* done,
+                          long long* lengths, float* hist_scores, long long* back, long long* toks, long long* order, int* anc, int S,
+                          long long* step_next, void* ticket, const float* emb, int emb_rows, const float* pe, int pe_rows,
+                          void* x_next, int D, int T_cap, const float* cand_gam, const float* cand_psi, float* gam, float* psi,
+                          int* last, unsigned char* frozen);
+
+/* Greedy CTC decoding: out int32 [R] = arg-max of logits[r][:V] (lower id on ties). */
+int st_ctc_best_path(st_stream_t stream, const float* logits, int ldl, int R, int V, int* out);
 
 /* Beam-search decode (transformer/Decode.py with a KV cache): cache bf16 [L][n][S][W]; for every layer, position
    t <= *step (device scalar) and utterance (beam consecutive hypothesis rows), row u*beam+s <- row order[u*beam+s]

@@ -1,0 +1,124 @@
+"""Joint CTC / attention beam search (Watanabe et al. 2017, "Hybrid CTC/Attention Architecture for End-to-End Speech
+Recognition", Algorithm 2) on the device: the CTC head's log-probabilities of one batch and the CTC prefix scorer's state,
+for ``transformer.Decode`` (``Decode(opt, device, model, ctc_head=...)`` with ``opt.ctc_weight > 0``).
+
+Once per batch: the head's logits over the packed encoder rows (one ``st_gemm`` against its padded bf16 weight), then
+``st_ctc_vocab_lp`` -> the vocabulary-major table ``lpT`` f32 [B, V, T_cap] and ``st_ctc_prefix_init`` -> the empty prefix
+in every beam slot.  Per decode step (inside the captured step): ``st_beam_pre_beam`` (the K best attention tokens of every
+hypothesis), ``st_ctc_prefix_score`` (their CTC prefix increments and states), ``st_beam_advance_joint`` (the top ``beam``
+of the joint scores, Beam.advance's bookkeeping, and the survivors' CTC state)."""
+import math
+
+import torch
+
+from . import native as nv
+
+F32, I32, I64 = torch.float32, torch.int32, torch.int64
+
+CHUNKS = (1, 2, 4, 8, 12, 16, 24, 32)        # frames per lane of st_ctc_prefix_score: T_cap = 64 x one of these
+
+
+def frame_capacity(t_max: int) -> int:
+    """T_cap of a batch whose longest utterance has ``t_max`` frames."""
+    for ch in CHUNKS:
+        if 64 * ch >= t_max:
+            return 64 * ch
+    raise ValueError("joint CTC decoding: %d frames exceed the prefix scorer's %d" % (t_max, 64 * CHUNKS[-1]))
+
+
+def pre_beam_width(opt, beam: int) -> int:
+    K = getattr(opt, "ctc_pre_beam", None)
+    return int(math.ceil(1.5 * beam)) if K is None else int(K)
+
+
+def _same_device(a, b) -> bool:
+    a, b = torch.device(a), torch.device(b)
+    if a.type != b.type:
+        return False
+    if a.type != "cuda":
+        return True
+    ia = a.index if a.index is not None else torch.cuda.current_device()
+    ib = b.index if b.index is not None else torch.cuda.current_device()
+    return ia == ib
+
+
+def check_options(opt, beam: int, head, model, device):
+    """-> (ctc_weight, K) of a joint search, or (0.0, None) for the attention-only path; ValueError on a bad combination."""
+    w = float(getattr(opt, "ctc_weight", None) or 0.0)
+    if not 0.0 <= w < 1.0:
+        raise ValueError("Decode: ctc_weight must lie in [0, 1), got %r" % w)
+    if head is not None:
+        W = head.ctc_proj.weight
+        d = model.decoder.d_model
+        if W.shape[1] != d:
+            raise ValueError("Decode: the CTC head's input width %d differs from d_model %d" % (W.shape[1], d))
+        if W.shape[0] != model.vocab_size:
+            raise ValueError("Decode: the CTC head's vocabulary %d differs from the decoder's %d" % (W.shape[0], model.vocab_size))
+        if not _same_device(W.device, device):
+            raise ValueError("Decode: the CTC head lives on %s, the decoder on %s" % (W.device, device))
+    if head is None or w == 0.0:
+        return 0.0, None
+    K = pre_beam_width(opt, beam)
+    if K < beam or K > 64:
+        raise ValueError("Decode: ctc_pre_beam must lie in [beam_size, 64] = [%d, 64], got %d" % (beam, K))
+    if K > model.vocab_size:
+        raise ValueError("Decode: ctc_pre_beam %d exceeds the vocabulary %d" % (K, model.vocab_size))
+    return w, K
+
+
+def head_logits(head, enc):
+    """The CTC head over packed encoder rows (bf16 [R, d]) -> f32 [R, v_pad] (padding columns at -1e30)."""
+    V, d = head.ctc_proj.weight.shape
+    v_pad = (V + 1 + 7) // 8 * 8
+    wb = torch.zeros(v_pad, d, dtype=torch.bfloat16, device=enc.device)
+    bias = torch.full((v_pad,), -1e30, dtype=F32, device=enc.device)
+    wb[:V].copy_(head.ctc_proj.weight.detach())
+    bias[:V].copy_(head.ctc_proj.bias.detach())
+    logits = torch.empty(enc.shape[0], v_pad, dtype=F32, device=enc.device)
+    nv.gemm(enc, wb, logits, epi=nv.EPI_F32, bias=bias)
+    return logits
+
+
+class CtcSearch(object):
+    """The CTC side of one joint search (or joint teacher-forced scoring) over B utterances x ``beam`` hypotheses."""
+
+    def __init__(self, head, enc, in_rows, beam: int, K: int, weight: float):
+        dev = enc.device
+        V = head.ctc_proj.weight.shape[0]
+        B = in_rows.B
+        self.V, self.B, self.beam, self.K, self.weight, self.blank = V, B, beam, K, float(weight), int(head.blank)
+        self.len = in_rows.len
+        self.T_cap = frame_capacity(int(in_rows.max_len))
+        n = B * beam
+        logits = head_logits(head, enc)
+        self.lpT = torch.empty(B, V, self.T_cap, dtype=F32, device=dev)
+        lse = torch.empty(logits.shape[0], dtype=F32, device=dev)
+        nv.ctc_vocab_lp(logits, V, in_rows.off, in_rows.len, self.T_cap, lse, self.lpT)
+        del logits
+        self.gam = torch.empty(n, 2, self.T_cap, dtype=F32, device=dev)
+        self.psi = torch.empty(n, dtype=F32, device=dev)
+        self.last = torch.empty(n, dtype=I32, device=dev)
+        self.frozen = torch.empty(n, dtype=torch.bool, device=dev)
+        nv.ctc_prefix_init(self.lpT, self.len, beam, self.blank, self.gam, self.psi, self.last, self.frozen)
+        self.ids = torch.zeros(n, K, dtype=I32, device=dev)
+        self.lp = torch.zeros(n, K, dtype=F32, device=dev)
+        self.cand_gam = torch.full((n, K, 2, self.T_cap), float("-inf"), dtype=F32, device=dev)
+        self.cand_psi = torch.zeros(n, K, dtype=F32, device=dev)
+        self.delta = torch.zeros(n, K, dtype=F32, device=dev)
+        self.ticket = torch.zeros(1, dtype=I64, device=dev)
+
+    def state(self):
+        return (self.cand_gam, self.cand_psi, self.gam, self.psi, self.last, self.frozen)
+
+    def score(self, eos, done):
+        """st_ctc_prefix_score of the candidates in ``ids``."""
+        nv.ctc_prefix_score(self.lpT, self.len, self.beam, self.blank, eos, self.ids, self.gam, self.psi, self.last, self.frozen, done,
+                            self.cand_gam, self.cand_psi, self.delta)
+
+    def advance(self, st, logits, V, eos, anc, advance_step, embed):
+        """One joint Beam.advance for every utterance: pre-beam, prefix scores, joint top-``beam`` + state moves."""
+        nv.beam_pre_beam(logits, V, self.ids, self.lp)
+        self.score(eos, st.done)
+        nv.beam_advance_joint(self.ids, self.lp, self.delta, self.weight, st.beam, st.step, eos, st.scores, st.tokens, st.done,
+                              st.lengths, st.hist_scores, st.back, st.toks, st.order, anc=anc, advance_step=advance_step,
+                              ticket=self.ticket, embed=embed, ctc=self.state())

@@ -122,6 +122,17 @@ SIGNATURES = {
     "st_beam_advance": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p,
                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p,
                         _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int],
+    "st_ctc_vocab_lp": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p],
+    "st_ctc_prefix_init": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p,
+                           _c_void_p],
+    "st_ctc_prefix_score": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int,
+                            _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "st_beam_pre_beam": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p],
+    "st_beam_advance_joint": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_float, _c_int, _c_int, _c_void_p, _c_int,
+                              _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                              _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int,
+                              _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "st_ctc_best_path": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
     "st_ce_fwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p],
     "st_ce_bwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p,
                   _c_void_p, _c_int],
@@ -212,7 +223,7 @@ def lib_path() -> str:
     return _build.LIB
 
 
-ABI_VERSION = 4      # == ST_ABI_VERSION in include/st_hip.h == st_version() of the library this binding was written against
+ABI_VERSION = 5      # == ST_ABI_VERSION in include/st_hip.h == st_version() of the library this binding was written against
 
 
 def load(build_if_missing: bool = True):
@@ -1238,6 +1249,122 @@ def beam_work_words(B: int, beam: int) -> int:
     """int64 elements of beam_advance's ``work`` scratch (zero-initialised): beam keys per hypothesis row, the step ticket, a
     ticket per utterance."""
     return B * beam * beam + 1 + B
+
+
+# ---- joint CTC / attention beam search (csrc/st_ctc_decode.hip) ---------------------------------------------------------------
+def _dev(t, dtype, shape, name):
+    if t is None or not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError("%s: expected a contiguous %s %s tensor on the GPU" % (name, dtype, list(shape)))
+    return t.data_ptr()
+
+
+def ctc_vocab_lp(logits, V, off, length, T_cap, lse, lpT):
+    """CTC logits f32 [R, >= V] (packed encoder rows, utterance b at off[b] .. off[b] + len[b]) -> lse f32 [R] and the
+    vocabulary-major log-probabilities lpT f32 [B, V, T_cap] (frames past len[b]: 0) - see st_ctc_vocab_lp."""
+    _mat(logits, F32, "logits")
+    R, B = logits.shape[0], off.numel()
+    _vec(off, I32, B, "off"), _vec(length, I32, B, "len")
+    _dev(lse, F32, (R,), "ctc_vocab_lp: lse"), _dev(lpT, F32, (B, V, T_cap), "ctc_vocab_lp: lpT")
+    _tag("ctc_vocab_lp", R, V, T_cap, io=(2 * 4.0 * R * V, lpT))
+    _check(load().st_ctc_vocab_lp(_stream(), logits.data_ptr(), logits.stride(0), R, int(V), off.data_ptr(), length.data_ptr(), B,
+                                  int(T_cap), lse.data_ptr(), lpT.data_ptr()), "st_ctc_vocab_lp")
+
+
+def ctc_prefix_init(lpT, length, beam, blank, gam, psi, last, frozen):
+    """The empty prefix's CTC state in every beam slot (see st_ctc_prefix_init): gam f32 [B * beam, 2, T_cap], psi f32, last
+    i32, frozen bool [B * beam]."""
+    B, V, T_cap = lpT.shape
+    n = B * beam
+    _dev(lpT, F32, (B, V, T_cap), "lpT"), _vec(length, I32, B, "len"), _dev(gam, F32, (n, 2, T_cap), "gam")
+    _dev(psi, F32, (n,), "psi"), _dev(last, I32, (n,), "last"), _dev(frozen, torch.bool, (n,), "frozen")
+    _check(load().st_ctc_prefix_init(_stream(), lpT.data_ptr(), V, T_cap, length.data_ptr(), B, int(beam), int(blank), gam.data_ptr(),
+                                     psi.data_ptr(), last.data_ptr(), frozen.data_ptr()), "st_ctc_prefix_init")
+
+
+def ctc_prefix_score(lpT, length, beam, blank, eos, cand, gam, psi, last, frozen, done, cand_gam, cand_psi, delta):
+    """CTC prefix scores of every hypothesis's K candidates (i32 [n, K]): cand_psi / delta f32 [n, K], the candidates' states
+    cand_gam f32 [n, K, 2, T_cap] - see st_ctc_prefix_score.  ``done``: bool [B] or None (no utterance skipped)."""
+    B, V, T_cap = lpT.shape
+    n = B * beam
+    K = cand.shape[1]
+    _dev(lpT, F32, (B, V, T_cap), "lpT"), _vec(length, I32, B, "len"), _dev(cand, I32, (n, K), "cand")
+    _dev(gam, F32, (n, 2, T_cap), "gam"), _dev(psi, F32, (n,), "psi"), _dev(last, I32, (n,), "last")
+    _dev(frozen, torch.bool, (n,), "frozen"), _dev(cand_gam, F32, (n, K, 2, T_cap), "cand_gam")
+    _dev(cand_psi, F32, (n, K), "cand_psi"), _dev(delta, F32, (n, K), "delta")
+    if done is not None:
+        _dev(done, torch.bool, (B,), "done")
+    _tag("ctc_prefix_score", n, K, T_cap, io=(4.0 * n * K * T_cap, 8.0 * n * T_cap, 8.0 * n * K * T_cap))
+    _check(load().st_ctc_prefix_score(_stream(), lpT.data_ptr(), V, T_cap, length.data_ptr(), B, int(beam), int(blank), int(eos),
+                                      cand.data_ptr(), K, gam.data_ptr(), psi.data_ptr(), last.data_ptr(), frozen.data_ptr(),
+                                      _p(done), cand_gam.data_ptr(), cand_psi.data_ptr(), delta.data_ptr()), "st_ctc_prefix_score")
+
+
+def beam_pre_beam(logits, V, ids, lp):
+    """Log-softmax of every decoder logits row (f32 [n, >= V]) and its K best -> ids i32 [n, K], lp f32 [n, K] (best first) -
+    see st_beam_pre_beam."""
+    _mat(logits, F32, "logits")
+    n, K = ids.shape
+    _dev(ids, I32, (n, K), "ids"), _dev(lp, F32, (n, K), "lp")
+    if logits.shape[0] != n:
+        raise ValueError("beam_pre_beam: logits rows %d != ids rows %d" % (logits.shape[0], n))
+    _tag("beam_pre_beam", n, V, K, io=((logits, n),))
+    _check(load().st_beam_pre_beam(_stream(), logits.data_ptr(), logits.stride(0), int(V), n, K, ids.data_ptr(), lp.data_ptr()),
+           "st_beam_pre_beam")
+
+
+def beam_advance_joint(ids, lp, delta, ctc_weight, beam, step, eos, scores, tokens, done, lengths, hist_scores, back, toks, order,
+                       anc=None, advance_step=False, ticket=None, embed=None, ctc=None):
+    """st_beam_advance over beam x K joint candidates (ids i32 / lp / delta f32 [B * beam, K]; score increment
+    (1 - w) lp + w delta).  State tensors as beam_advance.  ``advance_step`` needs ``ticket`` (zeroed i64 [1]).  ``embed`` as
+    beam_advance.  ``ctc`` = (cand_gam, cand_psi, gam, psi, last, frozen): the CTC state of the new hypotheses is moved in the
+    same launch - see st_beam_advance_joint."""
+    B = scores.shape[0]
+    n, K = ids.shape
+    _dev(ids, I32, (B * beam, K), "ids"), _dev(lp, F32, (n, K), "lp"), _dev(delta, F32, (n, K), "delta")
+    for t, dt, m, name in ((scores, F32, B * beam, "scores"), (tokens, I64, B * beam, "tokens"), (lengths, I64, B, "lengths"),
+                           (order, I64, B * beam, "order"), (step, I64, 1, "step")):
+        _vec(t, dt, m, name)
+    _dev(done, torch.bool, (B,), "done")
+    S = hist_scores.shape[0]
+    for t, dt, name in ((hist_scores, F32, "hist_scores"), (back, I64, "back"), (toks, I64, "toks")):
+        _dev(t, dt, (S, B, beam), name)
+    if advance_step and ticket is None:
+        raise ValueError("beam_advance_joint: advance_step needs the ticket word")
+    if ticket is not None:
+        _vec(ticket, I64, 1, "ticket")
+    emb = pe = x_next = None
+    if embed is not None:
+        emb, pe, x_next = embed
+        if not (emb.is_cuda and emb.dtype == F32 and emb.is_contiguous() and pe.is_cuda and pe.dtype == F32 and pe.is_contiguous()
+                and emb.dim() == 2 and pe.dim() == 2 and emb.shape[1] == pe.shape[1] and x_next.is_cuda and x_next.dtype == BF16
+                and x_next.is_contiguous() and tuple(x_next.shape) == (B * beam, emb.shape[1])):
+            raise ValueError("beam_advance_joint: embed = (emb f32 [V', D], pe f32 [P, D], x_next bf16 [B * beam, D]), contiguous")
+    T_cap, cp = 0, [None] * 6
+    if ctc is not None:
+        cand_gam, cand_psi, gam, psi, last, frozen = ctc
+        T_cap = gam.shape[2]
+        _dev(cand_gam, F32, (n, K, 2, T_cap), "cand_gam"), _dev(cand_psi, F32, (n, K), "cand_psi")
+        _dev(gam, F32, (n, 2, T_cap), "gam"), _dev(psi, F32, (n,), "psi"), _dev(last, I32, (n,), "last")
+        _dev(frozen, torch.bool, (n,), "frozen")
+        cp = [t.data_ptr() for t in ctc]
+    _tag("beam_advance_joint", B, beam, K)
+    _check(load().st_beam_advance_joint(_stream(), ids.data_ptr(), lp.data_ptr(), delta.data_ptr(), K, float(ctc_weight), int(beam), B,
+                                        step.data_ptr(), int(eos), scores.data_ptr(), tokens.data_ptr(), done.data_ptr(),
+                                        lengths.data_ptr(), hist_scores.data_ptr(), back.data_ptr(), toks.data_ptr(), order.data_ptr(),
+                                        _lineage(anc, B * beam, anc.shape[1] if anc is not None and anc.dim() == 2 else 0,
+                                                 "beam_advance_joint"),
+                                        int(anc.shape[1]) if anc is not None else 0, step.data_ptr() if advance_step else None,
+                                        _p(ticket), _p(emb), 0 if emb is None else emb.shape[0], _p(pe), 0 if pe is None else pe.shape[0],
+                                        _p(x_next), 0 if emb is None else emb.shape[1], int(T_cap), *cp), "st_beam_advance_joint")
+
+
+def ctc_best_path(logits, V, out):
+    """out i32 [R] = the arg-max of every CTC logits row (f32 [R, >= V]) - see st_ctc_best_path."""
+    _mat(logits, F32, "logits")
+    _dev(out, I32, (logits.shape[0],), "ctc_best_path: out")
+    _check(load().st_ctc_best_path(_stream(), logits.data_ptr(), logits.stride(0), logits.shape[0], int(V), out.data_ptr()),
+           "st_ctc_best_path")
+    return out
 
 
 def cache_reorder(cache, order, step, beam):

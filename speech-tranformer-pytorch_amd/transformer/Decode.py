@@ -25,6 +25,7 @@ import math
 import torch
 
 import transformer.Constants as Constants
+from st_amd import ctc_decode
 from st_amd import functional as F_
 from st_amd import native as nv
 from st_amd.arena import arena_of
@@ -37,12 +38,18 @@ LN_EPS = 1e-6
 class Decode(object):
     ''' Beam search over a trained Transformer. '''
 
-    def __init__(self, opt, device, model=None):
-        """opt: attribute-style (beam_size, n_best, [max_steps=100], [use_graph]); model: a transformer.Models.Transformer
-        on ``device`` (the reference loads a checkpoint here with an API that no longer exists)."""
+    def __init__(self, opt, device, model=None, ctc_head=None):
+        """opt: attribute-style (beam_size, n_best, [max_steps=100], [use_graph], [ctc_weight=0.0], [ctc_pre_beam]); model: a
+        transformer.Models.Transformer on ``device`` (the reference loads a checkpoint here with an API that no longer exists).
+        ``ctc_head``: the ``transformer.Loss.CTCAttentionLoss`` a joint model was trained with (its ``ctc_proj`` over the encoder
+        output).  With a head and ``opt.ctc_weight`` = w > 0 the search is the joint CTC / attention beam search (see
+        st_amd.ctc_decode): a token c of the ``ctc_pre_beam`` (default ceil(1.5 beam)) best attention tokens of hypothesis g
+        scores (1 - w) log p_att(c | g) + w (psi(g.c) - psi(g)), psi = the CTC prefix log-probability; every other token -inf."""
         if model is None:
             raise NotImplementedError("Decode(HIP): pass the Transformer instance (the reference's checkpoint loader "
                                       "calls an obsolete constructor and cannot run)")
+        self.ctc_weight, self.ctc_pre_beam = ctc_decode.check_options(opt, int(opt.beam_size), ctc_head, model, device)
+        self.ctc_head = ctc_head
         self.opt, self.device = opt, device
         self.model = model.to(device).eval()
         self.max_steps = int(getattr(opt, "max_steps", None) or 100)
@@ -138,10 +145,13 @@ class Decode(object):
         follow the back-pointers - through the lineage table the same launch maintains (``st.anc``: the cache rows stay
         where they were written), or, on the fall-back attention path, by permuting the caches - and the step counter
         advances."""
-        nv.beam_advance(logits, self.model.vocab_size, st.beam, st.step, Constants.EOS, st.scores, st.tokens, st.done,
-                        st.lengths, st.hist_scores, st.back, st.toks, st.order, work=st.beam_work, anc=st.anc,
-                        advance_step=st.anc is not None,
-                        embed=(self.model.decoder._st.emb, self.model.decoder._st.pe, st.x_in) if st.x_in is not None else None)
+        embed = (self.model.decoder._st.emb, self.model.decoder._st.pe, st.x_in) if st.x_in is not None else None
+        if st.ctc is not None:     # joint CTC / attention: pre-beam, CTC prefix scores, the joint advance (st_amd.ctc_decode)
+            st.ctc.advance(st, logits, self.model.vocab_size, Constants.EOS, st.anc, st.anc is not None, embed)
+        else:
+            nv.beam_advance(logits, self.model.vocab_size, st.beam, st.step, Constants.EOS, st.scores, st.tokens, st.done,
+                            st.lengths, st.hist_scores, st.back, st.toks, st.order, work=st.beam_work, anc=st.anc,
+                            advance_step=st.anc is not None, embed=embed)
         if st.anc is None:         # (with the lineage table the cache rows stay where they were written, and the merge
             nv.cache_reorder(st.caches, st.order, st.step, st.beam)             # launch has advanced the step counter)
             st.step.add_(1)
@@ -165,8 +175,9 @@ class Decode(object):
         cur.wait_stream(self._side)
         return out
 
-    def _init_state(self, src_batch, beam, arena, search=True):
-        """Encoder pass + the device state of a search over ``beam`` hypotheses per utterance (call inside ``arena.scope()``)."""
+    def _init_state(self, src_batch, beam, arena, search=True, ctc=None):
+        """Encoder pass + the device state of a search over ``beam`` hypotheses per utterance (call inside ``arena.scope()``).
+        ``ctc`` = (pre-beam width K, weight): also the CTC side of a joint search (st_amd.ctc_decode.CtcSearch)."""
         inputs, in_len = src_batch
         model, dev = self.model, self.device
         inputs = inputs.to(dev)
@@ -179,6 +190,7 @@ class Decode(object):
             raise ValueError("Decode: max_steps %d exceeds the decoder's positional-encoding table" % S)
         st = _DecodeState()
         st.B, st.beam, st.n = B, beam, n
+        st.ctc = None if ctc is None else ctc_decode.CtcSearch(self.ctc_head, enc, in_rows, beam, ctc[0], ctc[1])
         st.chains = dec.row_chains(arena)          # None: the layers do not fit the row-chain kernel
         st.need_c_len = not (dec.d_model // dec.layer_stack[0].slf_attn.n_head == 64 and self.max_steps <= 128)
         st.cross = []
@@ -219,19 +231,31 @@ class Decode(object):
         return st
 
     @torch.no_grad()
-    def score_hypotheses(self, src_batch, hyps):
+    def score_hypotheses(self, src_batch, hyps, ctc_weight=None):
         """Teacher-forced log-probability of ONE given token list per utterance, computed by the DECODE path (the step
         kernels of ``decode_batch``: KV cache, shared encoder keys, row chains) with the search switched off - the tokens
         are fed, not chosen.  -> tensor [B] fp32.  Not in the reference (its Decode has no scoring entry point): this is what
         lets the decode kernels be held to the fp64 oracle WITHOUT the selection bias of an arg-max over noisy scores
-        (tests/test_decode_cpu.py::run_decode), and it rescores n-best lists."""
+        (tests/test_decode_cpu.py::run_decode), and it rescores n-best lists.
+        ``ctc_weight`` = w (needs the CTC head): the JOINT score of the search, sum over the tokens of
+        (1 - w) log p_att + w (psi(prefix + token) - psi(prefix)) through the joint search's own kernels (st_ctc_prefix_score,
+        st_beam_advance_joint with the token fed as the only candidate) - for a hypothesis that ends in EOS
+        (1 - w) sum log p_att + w log p_ctc(hypothesis without EOS)."""
         B = src_batch[0].shape[0]
         assert len(hyps) == B and all(len(h) <= self.max_steps for h in hyps)
         V, dev = self.model.vocab_size, self.device
+        joint = ctc_weight is not None
+        if joint:
+            w = float(ctc_weight)
+            if not 0.0 <= w < 1.0:
+                raise ValueError("score_hypotheses: ctc_weight must lie in [0, 1), got %r" % w)
+            if self.ctc_head is None:
+                raise ValueError("score_hypotheses: ctc_weight needs the CTC head (Decode(..., ctc_head=...))")
         arena = arena_of(self.model)
         total = torch.zeros(B, dtype=torch.float64, device=dev)
+        ctc_total = torch.zeros(B, dtype=torch.float64, device=dev)
         with arena.scope():
-            st = self._init_state(src_batch, 1, arena, search=False)
+            st = self._init_state(src_batch, 1, arena, search=False, ctc=(1, w) if joint else None)
             steps = max(len(h) for h in hyps)
             fed = torch.full((steps, B), Constants.PAD, dtype=torch.long)
             live = torch.zeros(steps, B, dtype=torch.float64)
@@ -242,11 +266,47 @@ class Decode(object):
             for t in range(steps):
                 lp = torch.log_softmax(self._step(st)[:, :V].double(), -1)
                 total += lp.gather(1, fed[t].unsqueeze(1)).squeeze(1) * live[t]
+                if joint:                               # the fed token as the only candidate of the joint kernels
+                    cs = st.ctc
+                    cs.ids.copy_(fed[t].unsqueeze(1))
+                    cs.lp.copy_(lp.gather(1, fed[t].unsqueeze(1)))
+                    cs.score(Constants.EOS, None)
+                    ctc_total += torch.where(live[t] > 0, cs.delta[:, 0].double(), torch.zeros_like(ctc_total))
+                    nv.beam_advance_joint(cs.ids, cs.lp, cs.delta, cs.weight, 1, st.step, Constants.EOS, st.scores, st.tokens,
+                                          st.done, st.lengths, st.hist_scores, st.back, st.toks, st.order, ctc=cs.state())
                 st.tokens.copy_(fed[t])                 # beam 1: no back-pointers, the cache row stays where it is
                 st.step.add_(1)
                 if st.need_c_len:
                     st.c_len.add_(1)
+        if joint and w > 0.0:
+            return ((1.0 - w) * total + w * ctc_total).float()
         return total.float()
+
+    @torch.no_grad()
+    def ctc_greedy(self, src_batch):
+        """Greedy CTC decoding with the CTC head: per utterance the frame arg-max of its CTC logits (``st_ctc_best_path``),
+        repeats collapsed and blanks dropped -> list of B label lists."""
+        if self.ctc_head is None:
+            raise ValueError("ctc_greedy: needs the CTC head (Decode(..., ctc_head=...))")
+        inputs, in_len = src_batch
+        model, dev = self.model, self.device
+        inputs = inputs.to(dev)
+        t_max = int(in_len.max())
+        with arena_of(model).scope():
+            enc, in_rows = model.encoder.forward_rows(inputs[:, :t_max], in_len)
+            logits = ctc_decode.head_logits(self.ctc_head, enc)
+            best = nv.ctc_best_path(logits, self.ctc_head.ctc_proj.weight.shape[0],
+                                    torch.empty(logits.shape[0], dtype=I32, device=dev)).cpu().tolist()
+        blank, out, o = int(self.ctc_head.blank), [], 0
+        for T in in_len.tolist():
+            labels, prev = [], None
+            for k in best[o:o + int(T)]:
+                if k != prev and k != blank:
+                    labels.append(k)
+                prev = k
+            out.append(labels)
+            o += int(T)
+        return out
 
     def _decode_batch(self, src_batch):
         inputs, in_len = src_batch
@@ -254,7 +314,8 @@ class Decode(object):
         B, beam, n_best = inputs.shape[0], int(self.opt.beam_size), int(self.opt.n_best)
         arena = arena_of(model)
         with arena.scope():
-            st = self._init_state(src_batch, beam, arena)
+            st = self._init_state(src_batch, beam, arena,
+                                  ctc=(self.ctc_pre_beam, self.ctc_weight) if self.ctc_pre_beam is not None else None)
             S = self.max_steps
 
             def one_step():
