@@ -31,9 +31,9 @@ extern "C" {
 typedef void* st_stream_t; /* hipStream_t */
 
 /* Library ABI version, bumped on any signature change (2: round 5's k_prescaled / dense attention / grad_scale arguments;
- * 3, 4: round 6 - 4 added the column-sum workspace of st_row_chain_bwd).  A host binding must refuse a library whose st_version() differs from the header it was written against:
+ * 3, 4: round 6 - 4 added the column-sum workspace of st_row_chain_bwd; 5: the joint CTC / attention beam search; 6: st_ctc_loss_*).  A host binding must refuse a library whose st_version() differs from the header it was written against:
  * through ctypes / dlsym a stale libst_hip.so would be called with shifted arguments (st_amd/native.py: ABI_VERSION). */
-#define ST_ABI_VERSION 5
+#define ST_ABI_VERSION 6
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -507,7 +507,7 @@ int st_ce_bwd(st_stream_t stream, const float* logits, int ldl, int R, int V, co
               void* dlogits, int ldd);
 
 /* CTC head of the joint CTC + attention objective (BASELINE config 4; transformer/Loss.py:CTCAttentionLoss - the reference's
- * train_attn_and_ctc.py is empty, the head is the standard hybrid one).  ctc_loss itself stays in PyTorch-ROCm; these two
+ * train_attn_and_ctc.py is empty, the head is the standard hybrid one).  Around ctc_loss (PyTorch-ROCm, or st_ctc_loss_* below) these two
  * kernels stand where the [T, B, V] log-softmax tensor and its gradient would be.  logits f32 [R, ldl]: the ragged rows of
  * the encoder-side vocabulary projection (V valid columns; padding columns at -1e30 may be counted); rowmap i64 [R]: row r is
  * frame t of utterance b with rowmap[r] = b * T + t (negative: the row belongs to nobody); cols i32 [B, C]: the vocabulary
@@ -522,6 +522,26 @@ int st_ctc_gather(st_stream_t stream, const float* logits, int ldl, int R, int V
                   int C, float* lse, float* lp);
 int st_ctc_dlogits(st_stream_t stream, const float* logits, int ldl, int R, int V, const float* lse, const long long* rowmap, int T,
                    const float* roww, const int* scat, int C, const float* gsmall, const float* grad_out, void* dlogits, int ldd);
+
+/* CTC loss with lengths and labels on the DEVICE (csrc/st_ctc_loss.hip): nothing is read from host memory, so both launches can
+ * be captured into a HIP graph.  lp f32 [B, T, C]: log-probabilities over the utterance's small alphabet, class 0 = blank (what
+ * st_ctc_gather writes), C >= 2; classes i64 [B, L]: class indices into C (L <= 255; a label MAY be class 0: it is an ordinary
+ * label state that emits column 0 - one generic skip rule, s-2 -> s iff l'(s) != l'(s-2), covers it); in_len / tgt_len i32 [B]
+ * on the device (clamped to [0, T] / [0, L]; tgt_len 0 = the single blank state).  ws: st_ctc_loss_ws_kib(B, T, L) KiB (host
+ * query; -1: unsupported), holding alpha, beta (f32 [B, T, 2 L + 2] each, base-2 logarithms renormalised every 8 frames) and their f64 offsets.
+ * st_ctc_loss_fwd: nll f32 [B] = -log p(labels | lp), +inf where no alignment exists; one wave per (utterance, direction).
+ * st_ctc_loss_grad: g f32 [B, T, C] = coef[b] (exp(lp) - occ) for t < in_len[b], 0 past it - occ[b][t][k] the posterior
+ * probability that frame t emits class k (each frame's occupancies sum to 1), i.e. -coef occ is the exact derivative of
+ * coef nll with respect to lp and coef exp(lp) the log-softmax's share: the convention st_ctc_dlogits consumes; roww f32 [B] =
+ * coef[b].  softmax_term = 0 leaves the exp(lp) term out (g = -coef occ: what an autograd node over lp returns).  Where nll[b] is
+ * infinite g = 0 and roww[b] = 0 (zero_infinity).  The states of a class are accumulated in label
+ * order: no float atomics, bitwise reproducible. */
+int st_ctc_loss_ws_kib(int B, int T, int L);
+int st_ctc_loss_fwd(st_stream_t stream, const float* lp, int B, int T, int C, const long long* classes, int L, const int* in_len,
+                    const int* tgt_len, void* ws, long long ws_bytes, float* nll);
+int st_ctc_loss_grad(st_stream_t stream, const float* lp, int B, int T, int C, const long long* classes, int L, const int* in_len,
+                     const int* tgt_len, const float* coef, void* ws, long long ws_bytes, const float* nll, float* g, float* roww,
+                     int softmax_term);
 
 /* Attention probabilities of ONE attention sublayer, materialised (reference transformer/Attention.py:89,96: the `attns`
  * MultiHeadAttention.forward returns; Models.py:53-54,107-109 collect them under return_attns): P (f32 [B, H, Lq, Lk],

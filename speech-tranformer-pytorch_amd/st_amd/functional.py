@@ -659,7 +659,22 @@ class CtcPlan:
         self.roww = torch.zeros(B, dtype=F32, device=dev)                            # weight of utterance b's softmax term
         self.one = torch.ones(1, dtype=F32, device=dev)
         self.v_pad = v_pad
+        # the HIP CTC loss (native.ctc_loss_fwd / ctc_loss_grad) reads its lengths on the device
+        self.in_len_dev = self._il.clamp(0, self.T).to(I32)
+        self.tgt_len_dev = self._tl.clamp(0, L).to(I32)
+        self.nll = torch.zeros(B, dtype=F32, device=dev)
+        self.inv_btl = (1.0 / (B * self.tl.to(torch.float64))).to(F32)                # reduction='mean': 1 / (B max(tl, 1))
+        self.coef = self.inv_btl.clone()                                             # the joint step scales it by the CTC weight
+        self.ws = None                                                               # alpha / beta: loss_workspace()
 
+    def loss_workspace(self):
+        """The alpha / beta workspace of the HIP CTC loss (~26 MB at B = 32, T = 1,000, L = 50), allocated on first use - never
+        inside a capture: it would land in that graph's private pool while the plan outlives the graph."""
+        if self.ws is None:
+            if self.lp.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("CtcPlan.loss_workspace: first use inside a stream capture - call it before capturing")
+            self.ws = torch.empty(nv.ctc_loss_ws_bytes(self.B, self.T, self.L), dtype=torch.uint8, device=self.lp.device)
+        return self.ws
 
     def refresh_labels(self, targets) -> None:
         """(Re)derive everything that depends on the label VALUES, written in place: a loader that refills the same static
@@ -715,6 +730,51 @@ class CtcProjFn(torch.autograd.Function):
         dx = _empty(enc.shape[0], enc.shape[1], enc)
         dgrad(dl, head._st_wb, dx)
         return dx, None, None, None, None
+
+
+class CtcLossFn(torch.autograd.Function):
+    """Per-utterance CTC negative log-likelihood of ``lp`` (f32 [B, T, C] log-probabilities, class 0 = blank) for the class
+    sequences ``classes`` (i64 [B, L], L <= 255; a label may be class 0), lengths as DEVICE i32 tensors: csrc/st_ctc_loss.hip.
+    No host synchronisation and no host memory: capturable by torch.cuda.graph.  Utterances without an alignment come back as 0
+    (zero_infinity) with a zero gradient.
+
+    backward returns grad_out[b] * d nll[b] / d lp = -grad_out[b] * occ[b, t, k] (occ: the posterior probability that frame t
+    emits class k) - the TRUE derivative with respect to lp.  The ``exp(lp)`` term of the familiar ``softmax - occupancy`` form
+    belongs to the log-softmax that produced lp, and autograd adds it there; only the CTC head's fused path
+    (CTCAttentionLoss.ctc_rows -> st_ctc_dlogits) asks the kernel for both terms at once."""
+
+    @staticmethod
+    def forward(ctx, lp, classes, in_len, tgt_len):
+        lp = lp.contiguous()
+        B, T, _ = lp.shape
+        ws = torch.empty(nv.ctc_loss_ws_bytes(B, T, classes.shape[1]), dtype=torch.uint8, device=lp.device)
+        nll = torch.empty(B, dtype=F32, device=lp.device)
+        nv.ctc_loss_fwd(lp, classes, in_len, tgt_len, ws, nll)
+        ctx.save_for_backward(lp, classes, in_len, tgt_len, ws, nll)
+        return torch.nan_to_num(nll, nan=0.0, posinf=0.0)
+
+    @staticmethod
+    def backward(ctx, g_nll):
+        lp, classes, in_len, tgt_len, ws, nll = ctx.saved_tensors
+        g = torch.empty_like(lp)
+        nv.ctc_loss_grad(lp, classes, in_len, tgt_len, g_nll.to(F32).contiguous(), ws, nll, g, torch.empty_like(nll), softmax_term=False)
+        return g, None, None, None
+
+
+def ctc_loss(lp, classes, in_len, tgt_len, reduction="mean", zero_infinity=True):
+    """``torch.nn.functional.ctc_loss`` for batch-major log-probabilities with everything on the device (CtcLossFn): lp f32
+    [B, T, C] (blank = class 0), classes i64 [B, L], in_len / tgt_len i32 [B] GPU tensors.  reduction 'none' -> nll [B];
+    'mean' -> mean over utterances of nll / max(tgt_len, 1), as torch defines it.  Only zero_infinity=True is offered (an
+    utterance without an alignment contributes 0 and receives no gradient): the kernels never produce the NaN gradients of the
+    other setting."""
+    if not zero_infinity:
+        raise ValueError("ctc_loss: only zero_infinity=True is implemented")
+    if reduction not in ("mean", "none"):
+        raise ValueError("ctc_loss: reduction must be 'mean' or 'none', got %r" % (reduction,))
+    nll = CtcLossFn.apply(lp, classes, in_len, tgt_len)
+    if reduction == "none":
+        return nll
+    return (nll / tgt_len.clamp_min(1).to(nll.dtype)).mean()
 
 
 class AttnTap:

@@ -133,6 +133,10 @@ SIGNATURES = {
                               _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int,
                               _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "st_ctc_best_path": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
+    "st_ctc_loss_ws_kib": [_c_int, _c_int, _c_int],
+    "st_ctc_loss_fwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_ll, _c_void_p],
+    "st_ctc_loss_grad": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_ll,
+                         _c_void_p, _c_void_p, _c_void_p, _c_int],
     "st_ce_fwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p],
     "st_ce_bwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p,
                   _c_void_p, _c_int],
@@ -223,7 +227,7 @@ def lib_path() -> str:
     return _build.LIB
 
 
-ABI_VERSION = 5      # == ST_ABI_VERSION in include/st_hip.h == st_version() of the library this binding was written against
+ABI_VERSION = 6      # == ST_ABI_VERSION in include/st_hip.h == st_version() of the library this binding was written against
 
 
 def load(build_if_missing: bool = True):
@@ -1033,6 +1037,76 @@ def ctc_dlogits(logits, lse, rowmap, T, roww, scat, gsmall, grad_out, dlogits, V
     _check(load().st_ctc_dlogits(_stream(), logits.data_ptr(), logits.stride(0), R, V, lse.data_ptr(), rowmap.data_ptr(), int(T),
                                  roww.data_ptr(), scat.data_ptr(), C, gsmall.data_ptr(), grad_out.data_ptr(), dlogits.data_ptr(),
                                  dlogits.stride(0)), "st_ctc_dlogits")
+
+
+# ---- CTC loss with device-resident lengths (csrc/st_ctc_loss.hip) ---------------------------------------------------------------
+CTC_LOSS_MAX_L = 255      # four state pairs per lane of one wave
+
+
+def ctc_loss_ws_bytes(B, T, L) -> int:
+    """Bytes of the alpha / beta workspace st_ctc_loss_fwd / _grad want for lp [B, T, *] and classes [B, L] (a host-only query:
+    no launch, no GPU)."""
+    if L > CTC_LOSS_MAX_L or min(B, T, L) < 0:
+        raise ValueError("ctc_loss: at most %d labels per utterance are supported (got L = %d)" % (CTC_LOSS_MAX_L, L))
+    kib = int(load()._cdll.st_ctc_loss_ws_kib(int(B), int(T), int(L)))
+    if kib < 0:
+        raise ValueError("st_ctc_loss_ws_kib: unsupported shape B = %d, T = %d, L = %d" % (B, T, L))
+    return kib * 1024
+
+
+def _ctc_loss_args(who, lp, classes, in_len, tgt_len, ws, extra):
+    """The checks of ctc_loss_fwd / ctc_loss_grad, all BEFORE any launch (and before the library is loaded): ValueError for a
+    wrong dtype / shape / layout / size, RuntimeError for a tensor that is not on the GPU.  -> (B, T, C, L)"""
+    if lp.dim() != 3 or lp.dtype != F32 or not lp.is_contiguous():
+        raise ValueError("%s: lp must be a contiguous f32 [B, T, C] tensor, got %s %s" % (who, lp.dtype, tuple(lp.shape)))
+    B, T, C = lp.shape
+    if C < 2:
+        raise ValueError("%s: lp needs at least two classes (blank + one label), got C = %d" % (who, C))
+    if T < 1:
+        raise ValueError("%s: lp has no frames" % who)
+    if classes.dim() != 2 or classes.shape[0] != B or classes.dtype != I64 or not classes.is_contiguous():
+        raise ValueError("%s: classes must be a contiguous i64 [B, L] tensor, got %s %s" % (who, classes.dtype, tuple(classes.shape)))
+    L = classes.shape[1]
+    if L > CTC_LOSS_MAX_L:
+        raise ValueError("%s: at most %d labels per utterance are supported (got L = %d)" % (who, CTC_LOSS_MAX_L, L))
+    for name, t in (("in_len", in_len), ("tgt_len", tgt_len)):
+        if t.dtype != I32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous i32 [B] tensor, got %s %s" % (who, name, t.dtype, tuple(t.shape)))
+    for name, t, shape in extra:
+        if t.dtype != F32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous f32 %s tensor, got %s %s" % (who, name, list(shape), t.dtype, tuple(t.shape)))
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous():
+        raise ValueError("%s: ws must be a flat uint8 buffer (native.ctc_loss_ws_bytes)" % who)
+    for name, t in [("lp", lp), ("classes", classes), ("in_len", in_len), ("tgt_len", tgt_len), ("ws", ws)] + [(n, t) for n, t, _ in extra]:
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s must live on the GPU: the HIP path has no CPU fallback" % (who, name))
+    if ws.numel() < ctc_loss_ws_bytes(B, T, L):
+        raise ValueError("%s: ws holds %d bytes, %d are needed" % (who, ws.numel(), ctc_loss_ws_bytes(B, T, L)))
+    return B, T, C, L
+
+
+def ctc_loss_fwd(lp, classes, in_len, tgt_len, ws, nll):
+    """nll f32 [B] = -log p(classes | lp), +inf where no alignment exists; alpha and beta are left in ``ws`` for ctc_loss_grad -
+    see st_ctc_loss_fwd.  Lengths are DEVICE i32 tensors: nothing is read on the host (capturable)."""
+    B, T, C, L = _ctc_loss_args("ctc_loss_fwd", lp, classes, in_len, tgt_len, ws, [("nll", nll, (lp.shape[0],))])
+    _tag("ctc_loss_fwd", B, T, L, io=(lp, 16.0 * B * T * (L + 1)))
+    _check(load().st_ctc_loss_fwd(_stream(), lp.data_ptr(), B, T, C, classes.data_ptr(), L, in_len.data_ptr(), tgt_len.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), nll.data_ptr()), "st_ctc_loss_fwd")
+    return nll
+
+
+def ctc_loss_grad(lp, classes, in_len, tgt_len, coef, ws, nll, g, roww, softmax_term=True):
+    """g f32 [B, T, C] = coef[b] (exp(lp) - occ) on the frames below in_len[b], 0 past them; roww[b] = coef[b]; both 0 where
+    nll[b] is infinite - see st_ctc_loss_grad (after ctc_loss_fwd on the same lp / ws).  ``softmax_term=False``: g = -coef occ, the
+    derivative of coef * nll with respect to lp itself."""
+    Bn = lp.shape[0] if lp.dim() == 3 else 0
+    B, T, C, L = _ctc_loss_args("ctc_loss_grad", lp, classes, in_len, tgt_len, ws,
+                                [("coef", coef, (Bn,)), ("nll", nll, (Bn,)), ("g", g, tuple(lp.shape)), ("roww", roww, (Bn,))])
+    _tag("ctc_loss_grad", B, T, L, io=(lp, g, 16.0 * B * T * (L + 1)))
+    _check(load().st_ctc_loss_grad(_stream(), lp.data_ptr(), B, T, C, classes.data_ptr(), L, in_len.data_ptr(), tgt_len.data_ptr(),
+                                   coef.data_ptr(), ws.data_ptr(), ws.numel(), nll.data_ptr(), g.data_ptr(), roww.data_ptr(),
+                                   1 if softmax_term else 0), "st_ctc_loss_grad")
+    return g
 
 
 def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False):

@@ -514,25 +514,34 @@ class JointTrainStep:
     train_attn_and_ctc.py is an empty file - the step is train.py:25-46 with transformer/Loss.py:CTCAttentionLoss as the
     criterion):  loss = w * CTC(encoder output) + (1 - w) * CE(decoder logits).
 
-    Everything except ``ctc_loss`` itself runs as HIP kernels and, in graph mode, inside three captured graphs that share a
-    memory pool:
+    ``ctc="torch"`` (the default; environment ST_CTC_LOSS): everything except ``ctc_loss`` itself runs as HIP kernels and, in
+    graph mode, inside three captured graphs that share a memory pool:
       graph A1  zero_grad, encoder forward, the CTC head's projection over the ragged encoder rows and st_ctc_gather (the
                 <= L + 1 log-probabilities per frame ctc_loss reads - the [T, B, V] log-softmax tensor of the module-level
                 path is never built);
-      eager     ``torch.nn.functional.ctc_loss`` on that small tensor + its gradient, ON A SIDE STREAM (PyTorch-ROCm, as the
-                task prescribes for the loss heads; torch's CTC kernels build their length tables from pageable host memory,
-                which a stream capture refuses).  Its three kernels walk the 1,000 frames sequentially on 32 workgroups -
-                3.1 ms at config 2 with the chip idle beside them - so meanwhile the main stream replays
+      eager     ``torch.nn.functional.ctc_loss`` on that small tensor + its gradient, ON A SIDE STREAM (torch's CTC kernels
+                build their length tables from pageable host memory, which a stream capture refuses).  Its three kernels walk
+                the 1,000 frames sequentially on 32 workgroups - 3.1 ms at config 2 with the chip idle beside them - so
+                meanwhile the main stream replays
       graph A2  decoder forward, vocabulary projection + cross-entropy (one node), and the backward of that branch down to the
                 encoder output (the decoder never sees the CTC branch);
       graph B   (after the side stream's event) backward from BOTH roots into the encoder - the encoder output with the
                 decoder's gradient, the log-probabilities with w * ctc_loss's gradient (st_ctc_dlogits -> the head's backward
                 GEMMs) -, the deferred weight gradients, clip + Adam over the model's arena, the head's own Adam.
+
+    ``ctc="hip"``: the CTC loss is csrc/st_ctc_loss.hip - lengths and labels on the device, two launches (the alpha / beta
+    recursions, one wave per utterance and direction; the gradient), which write ``plan.g_lp`` / ``plan.roww`` themselves.
+    Nothing of the step touches host memory any more, so graph mode captures ONE graph on one stream - part A1, the two CTC
+    launches, part A2, part B - with no side stream and no events; eager mode runs the same sequence.
+
     One batch signature at a time (a new signature re-captures)."""
 
     def __init__(self, model: nn.Module, optimizer, head, max_grad_norm: float, head_optimizer=None, use_graph: bool = True,
-                 graph_warmup: int = 2):
+                 graph_warmup: int = 2, ctc: Optional[str] = None):
         self.model, self.optimizer, self.head, self.head_optimizer = model, optimizer, head, head_optimizer
+        self.ctc = os.environ.get("ST_CTC_LOSS", "torch") if ctc is None else ctc
+        if self.ctc not in ("torch", "hip"):
+            raise ValueError("JointTrainStep: ctc must be 'torch' or 'hip', got %r" % (self.ctc,))
         self.max_grad_norm, self.use_graph, self.graph_warmup = max_grad_norm, use_graph, graph_warmup
         self.global_step = 0
         self._sig, self._seen, self._cap, self._plan = None, 0, None, None
@@ -578,6 +587,8 @@ class JointTrainStep:
 
     def _ctc(self, lp, plan):
         w = float(self.head.ctc_weight)
+        if self.ctc == "hip":           # the gradient kernel writes w * g and the per-utterance softmax weights itself
+            return self.head.ctc_rows(lp, plan, impl="hip", fill_weight=w)[0]
         ctc, g = self.head.ctc_rows(lp, plan)
         plan.g_lp.copy_(g)
         plan.g_lp.mul_(w)
@@ -641,6 +652,8 @@ class JointTrainStep:
             self._keep = batch
         plan, layouts = self._plan, self._layouts
         self.optimizer.update_learning_rate(self.global_step)
+        if self.ctc == "hip":
+            return self._call_hip(batch, plan, layouts)
         main = torch.cuda.current_stream()
         if not self.use_graph or self._seen < self.graph_warmup:
             self._seen += 1
@@ -651,25 +664,7 @@ class JointTrainStep:
             gnorm = self._part_b(enc, enc_in, lp, plan)
             return self._joint(att, ctc), att, ctc, gnorm
         if self._cap is None:
-            # as TrainStep._capture: everything lazily created must exist BEFORE the capture - Adam's flat state (a captured
-            # zero-fill would reset it on every replay), the process-wide scratch the step's kernels share (split-K partials and
-            # tickets, the norm's block partials: inside a capture they would land in this graph's private pool), the seed
-            if hasattr(self.optimizer, "_flat_state") and getattr(self.optimizer, "arena", None) is not None:
-                self.optimizer._flat_state()
-            nv.splitk_scratch(inputs.device)
-            if hasattr(self.optimizer, "norm_scratch"):
-                self.optimizer.norm_scratch(inputs.device)
-            if self._seed is None or self._seed.device != inputs.device:
-                self._seed = torch.empty((), dtype=torch.float32, device=inputs.device)
-            if self.head_optimizer is not None:
-                groups = self.head_optimizer.param_groups
-                if not all(g.get("capturable", False) for g in groups):
-                    raise ValueError("JointTrainStep(use_graph=True): head_optimizer must be built with capturable=True "
-                                     "(its step is captured in graph B)")
-                if any(len(self.head_optimizer.state.get(q, {})) == 0 for g in groups for q in g["params"]):
-                    raise ValueError("JointTrainStep(use_graph=True): head_optimizer has no state yet - run at least one eager "
-                                     "step first (graph_warmup >= 1): state created inside the capture would be reset by "
-                                     "every replay")
+            self._before_capture(inputs.device)
             torch.cuda.synchronize()
             pool = torch.cuda.graph_pool_handle()
             ga1, ga2, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -687,3 +682,53 @@ class JointTrainStep:
         main.wait_event(done)
         gb.replay()
         return self._joint(att, ctc), att, ctc, gnorm
+
+    def _step_hip(self, batch, plan, layouts):
+        """The whole step as one sequence on the current stream (ctc="hip"): -> (joint loss, attention CE, CTC loss, clip norm)"""
+        enc, lp = self._part_a1(batch, plan, layouts)
+        ctc = self._ctc(lp, plan)
+        att, enc_in = self._part_a2(batch, enc, layouts)
+        gnorm = self._part_b(enc, enc_in, lp, plan)
+        return self._joint(att, ctc), att, ctc, gnorm
+
+    def _call_hip(self, batch, plan, layouts):
+        if not self.use_graph or self._seen < self.graph_warmup:
+            self._seen += 1
+            return self._step_hip(batch, plan, layouts)
+        if self._cap is None:
+            self._before_capture(batch[0].device)
+            plan.loss_workspace()                 # alpha / beta belong to the plan, not to the graph's pool
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                out = self._step_hip(batch, plan, layouts)
+            self._cap = (graph, out)
+        graph, out = self._cap
+        graph.replay()
+        return out
+
+    def _before_capture(self, device):
+        """As TrainStep._capture: everything lazily created must exist BEFORE the capture - Adam's flat state (a captured zero-fill
+        would reset it on every replay), the process-wide scratch the step's kernels share (split-K partials and tickets, the
+        norm's block partials: inside a capture they would land in this graph's private pool), the seed."""
+        if hasattr(self.optimizer, "_flat_state") and getattr(self.optimizer, "arena", None) is not None:
+            self.optimizer._flat_state()
+        nv.splitk_scratch(device)
+        if hasattr(self.optimizer, "norm_scratch"):
+            self.optimizer.norm_scratch(device)
+        if self._seed is None or self._seed.device != device:
+            self._seed = torch.empty((), dtype=torch.float32, device=device)
+        if self.head_optimizer is not None:
+            groups = self.head_optimizer.param_groups
+            if not all(g.get("capturable", False) for g in groups):
+                raise ValueError("JointTrainStep(use_graph=True): head_optimizer must be built with capturable=True "
+                                 "(its step is captured in graph B)")
+            if any(len(self.head_optimizer.state.get(q, {})) == 0 for g in groups for q in g["params"]):
+                raise ValueError("JointTrainStep(use_graph=True): head_optimizer has no state yet - run at least one eager "
+                                 "step first (graph_warmup >= 1): state created inside the capture would be reset by "
+                                 "every replay")
+
+    @property
+    def graphs(self):
+        """The captured graphs of the current batch signature (three with ctc="torch", one with ctc="hip"; none before a capture)."""
+        return [] if self._cap is None else [x for x in self._cap if isinstance(x, torch.cuda.CUDAGraph)]
