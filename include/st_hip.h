@@ -10,7 +10,7 @@
  *
  * Conventions
  *  - plain pointers and sizes only; all pointers are DEVICE pointers;
- *  - every call is asynchronous on `stream` (hipStream_t passed as void*),
+ *  - every call is asynchronous on `stream` (a hipStream_t),
  *    holds no global state and never synchronises the device (it is called
  *    from the autograd engine thread as well as the main thread);
  *  - return 0 on success, a positive hipError_t if the launch failed, a
@@ -28,11 +28,16 @@
 extern "C" {
 #endif
 
-typedef void* st_stream_t; /* hipStream_t */
+typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C: no HIP header needed */
 
 /* Library ABI version, bumped on any signature change (2: round 5's k_prescaled / dense attention / grad_scale arguments;
  * 3, 4: round 6 - 4 added the column-sum workspace of st_row_chain_bwd; 5: the joint CTC / attention beam search; 6: st_ctc_loss_*).  A host binding must refuse a library whose st_version() differs from the header it was written against:
- * through ctypes / dlsym a stale libst_hip.so would be called with shifted arguments (st_amd/native.py: ABI_VERSION). */
+ * through ctypes / dlsym a stale libst_hip.so would be called with shifted arguments.
+ * This header is the ONLY copy of the ABI: every source under csrc/ is compiled against it (csrc/st_common.cuh includes it, so a
+ * definition that disagrees with its declaration stops the build), st_version() returns this macro, and st_amd/native.py
+ * parses this file at import for its argument types, ABI_VERSION and the EPI_* constants.  To add an entry point: declare
+ * it here (parameter types: pointers, st_stream_t, int, unsigned, float, long, long long - the binding refuses anything
+ * else), define it in csrc/, write its wrapper in st_amd/native.py - and bump the number if an existing signature moved. */
 #define ST_ABI_VERSION 6
 int st_version(void);
 

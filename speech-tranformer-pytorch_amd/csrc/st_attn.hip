@@ -31,19 +31,19 @@
 #include "st_attn_common.cuh"
 
 // st_attn64.hip (AttnArgs passed by address: the type is local to each translation unit, the layout is shared)
-extern "C" int st_attn64_fwd_launch(hipStream_t stream, const void* args, int grid_x, int drop, int kpre);
+int st_attn64_fwd_launch(hipStream_t stream, const void* args, int grid_x, int drop, int kpre);
 // st_attn_xs.hip: few queries against many keys (the decoder-encoder attention), 64-wide heads
-extern "C" int st_attn_xs_fwd_launch(hipStream_t stream, const void* args, int grid_x, int drop, const void* f1, const void* self);
-extern "C" void st_attn_xs_self_args(void* out, const void* Q, const void* K, const void* V, int ld, void* O, void* Ores, int ldo,
-                                     float* lse, const unsigned* drop_seed, unsigned drop_salt, int drop_thresh, float drop_scale);
-extern "C" int st_attn_xs_self_args_size();
-extern "C" void st_attn_xs_f1_args(void* out, const void* A, int lda, const void* R, int ldr, const void* wfrag, int n_blocks,
-                                   int next_blocks, float eps, const float* bo, const float* g0, const float* be0, void* out0,
-                                   void* xhat0, float* rstd0, const float* bq, void* Qout, int ldq);
-extern "C" int st_attn_xs_f1_args_size();
-extern "C" int st_attn_xs_tile_rows();
+int st_attn_xs_fwd_launch(hipStream_t stream, const void* args, int grid_x, int drop, const void* f1, const void* self);
+void st_attn_xs_self_args(void* out, const void* Q, const void* K, const void* V, int ld, void* O, void* Ores, int ldo,
+                          float* lse, const unsigned* drop_seed, unsigned drop_salt, int drop_thresh, float drop_scale);
+int st_attn_xs_self_args_size();
+void st_attn_xs_f1_args(void* out, const void* A, int lda, const void* R, int ldr, const void* wfrag, int n_blocks,
+                        int next_blocks, float eps, const float* bo, const float* g0, const float* be0, void* out0,
+                        void* xhat0, float* rstd0, const float* bq, void* Qout, int ldq);
+int st_attn_xs_f1_args_size();
+int st_attn_xs_tile_rows();
 // st_attn_bwd64.hip: the hand-scheduled backward for long non-causal problems with 64-wide heads
-extern "C" int st_attn_bwd64_launch(hipStream_t stream, const void* a, const void* ak, int n_q, int n_k, int drop);
+int st_attn_bwd64_launch(hipStream_t stream, const void* a, const void* ak, int n_q, int n_k, int drop);
 
 namespace {
 

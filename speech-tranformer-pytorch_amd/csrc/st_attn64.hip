@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd64_kernel(AttnArgs a) {
 
 }  // namespace
 
-extern "C" int st_attn64_fwd_launch(hipStream_t stream, const void* args_, int grid_x, int drop, int kpre) {
+int st_attn64_fwd_launch(hipStream_t stream, const void* args_, int grid_x, int drop, int kpre) {
   const AttnArgs& a = *static_cast<const AttnArgs*>(args_);
   dim3 grid(grid_x), block(256);
   // (the dropout variant and the exact fall-back loop multiply by a.c2 = 1 when the keys are pre-scaled: one instantiation)

@@ -440,9 +440,9 @@ __global__ __launch_bounds__(512, 1) void attn_xs_fwd_kernel(AttnArgs a, XF1Args
 
 }  // namespace
 
-extern "C" int st_attn_xs_tile_rows() { return XQ; }
+int st_attn_xs_tile_rows() { return XQ; }
 
-extern "C" int st_attn_xs_fwd_launch(hipStream_t stream, const void* args_, int grid_x, int drop, const void* f1_, const void* self_) {
+int st_attn_xs_fwd_launch(hipStream_t stream, const void* args_, int grid_x, int drop, const void* f1_, const void* self_) {
   const AttnArgs& a = *static_cast<const AttnArgs*>(args_);
   dim3 grid(grid_x), block(512);
   XF1Args f = {};
@@ -463,20 +463,20 @@ extern "C" int st_attn_xs_fwd_launch(hipStream_t stream, const void* args_, int 
   return (int)hipGetLastError();
 }
 
-extern "C" void st_attn_xs_self_args(void* out, const void* Q, const void* K, const void* V, int ld, void* O, void* Ores, int ldo,
-                                     float* lse, const unsigned* drop_seed, unsigned drop_salt, int drop_thresh, float drop_scale) {
+void st_attn_xs_self_args(void* out, const void* Q, const void* K, const void* V, int ld, void* O, void* Ores, int ldo,
+                          float* lse, const unsigned* drop_seed, unsigned drop_salt, int drop_thresh, float drop_scale) {
   XSelfArgs s;
   s.Q = (const bf16*)Q; s.K = (const bf16*)K; s.V = (const bf16*)V; s.ld = ld; s.O = (bf16*)O; s.Ores = (bf16*)Ores; s.ldo = ldo; s.lse = lse;
   const bool on = drop_seed != nullptr && drop_thresh > 0;
   s.drop.seed = on ? drop_seed : nullptr; s.drop.salt = drop_salt; s.drop.thresh = on ? drop_thresh : 0; s.drop.scale = on ? drop_scale : 1.f;
   *static_cast<XSelfArgs*>(out) = s;
 }
-extern "C" int st_attn_xs_self_args_size() { return (int)sizeof(XSelfArgs); }
+int st_attn_xs_self_args_size() { return (int)sizeof(XSelfArgs); }
 
 // the F1 stage's arguments as st_attn.hip hands them over (the struct is local to this translation unit)
-extern "C" void st_attn_xs_f1_args(void* out, const void* A, int lda, const void* R, int ldr, const void* wfrag, int n_blocks,
-                                   int next_blocks, float eps, const float* bo, const float* g0, const float* be0, void* out0,
-                                   void* xhat0, float* rstd0, const float* bq, void* Qout, int ldq) {
+void st_attn_xs_f1_args(void* out, const void* A, int lda, const void* R, int ldr, const void* wfrag, int n_blocks,
+                        int next_blocks, float eps, const float* bo, const float* g0, const float* be0, void* out0,
+                        void* xhat0, float* rstd0, const float* bq, void* Qout, int ldq) {
   XF1Args f;
   f.A = (const bf16*)A; f.lda = lda; f.R = (const bf16*)R; f.ldr = ldr; f.wfrag = (const bf16x8*)wfrag;
   f.wave_frags = n_blocks * 16 + DEPTH; f.next_frags = next_blocks > 0 ? next_blocks * 16 + DEPTH : 0; f.eps = eps;
@@ -484,4 +484,4 @@ extern "C" void st_attn_xs_f1_args(void* out, const void* A, int lda, const void
   f.ldp = ldq;
   *static_cast<XF1Args*>(out) = f;
 }
-extern "C" int st_attn_xs_f1_args_size() { return (int)sizeof(XF1Args); }
+int st_attn_xs_f1_args_size() { return (int)sizeof(XF1Args); }

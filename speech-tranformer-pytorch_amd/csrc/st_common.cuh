@@ -34,6 +34,7 @@
 #endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "st_hip.h"   // the C ABI: every extern "C" definition in this directory is checked against its declaration
 
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

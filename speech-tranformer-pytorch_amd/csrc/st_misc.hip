@@ -1552,4 +1552,4 @@ extern "C" int st_clock_probe(hipStream_t stream, long long* out, int n_wg, int 
   return 0;
 }
 
-extern "C" int st_version(void) { return 6; }      // == ST_ABI_VERSION (include/st_hip.h) == native.ABI_VERSION
+extern "C" int st_version(void) { return ST_ABI_VERSION; }

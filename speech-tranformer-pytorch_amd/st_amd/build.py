@@ -2,7 +2,7 @@
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build
 container; the resulting .so travels to the GPU box with the source tree.
-Staleness is decided by a content hash of csrc/ stored next to the library
+Staleness is decided by a content hash of csrc/ and include/st_hip.h stored next to the library
 (file mtimes do not survive the copy to the GPU box).  Every source is compiled
 to its own object (in parallel; objects are cached by content hash under
 lib/obj/), then linked.
@@ -15,6 +15,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
+ABI_HEADER = os.path.join(INCLUDE, "st_hip.h")       # the one copy of the C ABI: the sources are compiled against it, native.py parses it
 LIBDIR = os.path.join(os.path.dirname(HERE), "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libst_hip.so")
@@ -22,7 +24,8 @@ STAMP = LIB + ".srchash"
 SOURCES = ["st_gemm_sym.hip", "st_wgrad.hip", "st_gemm_ws.hip", "st_gemm_ln.hip", "st_gemm_lnbwd.hip", "st_rowchain.hip", "st_attn.hip",
            "st_attn64.hip", "st_attn_bwd64.hip", "st_attn_xs.hip", "st_attn_dense.hip", "st_misc.hip",
            "st_ctc_decode.hip", "st_ctc_loss.hip"]
-FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-fPIC", "-Wno-unused-result"]
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-fPIC", "-Wno-unused-result",
+         "-I" + os.path.relpath(INCLUDE, CSRC)]      # (relative: hipcc runs in csrc/, and the flags are part of the source hash, which must not depend on where the checkout lies)
 # per-file additions (none today; a kernel that owns all 512 registers per lane would want "-mllvm -amdgpu-mfma-vgpr-form":
 # left to its heuristics the compiler then puts score accumulators into AGPRs and pays a v_accvgpr_read per score)
 EXTRA = {}
@@ -41,7 +44,8 @@ if os.environ.get("ST_DEV_TRACE") == "1":
 
 
 def _headers() -> bytes:
-    h = b""
+    with open(ABI_HEADER, "rb") as f:
+        h = b"st_hip.h" + f.read()
     for name in sorted(os.listdir(CSRC)):
         if name.endswith((".cuh", ".h", ".inc")):
             with open(os.path.join(CSRC, name), "rb") as f:
@@ -51,6 +55,8 @@ def _headers() -> bytes:
 
 def source_hash() -> str:
     h = hashlib.sha256(" ".join(FLAGS + sorted(sum(([k] + v for k, v in EXTRA.items()), []))).encode())
+    with open(ABI_HEADER, "rb") as f:
+        h.update(f.read())
     for name in sorted(os.listdir(CSRC)):
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(name.encode())

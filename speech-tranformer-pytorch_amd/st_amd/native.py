@@ -13,142 +13,54 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from typing import Optional
 
 import torch
 
 from . import build as _build
 
-EPI_BF16, EPI_BF16_RELU, EPI_F32, EPI_BF16_MASK, EPI_BF16_ADD, EPI_F32_ATOMIC, EPI_F32_ATOMIC_T, EPI_BF16_DELTA = range(8)
+_CTYPES = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "long": ctypes.c_long,
+           "long long": ctypes.c_longlong}
 
-_c_int, _c_float, _c_void_p, _c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong
-_c_uint = ctypes.c_uint
-_c_long = ctypes.c_long
 
-# name -> argtypes (restype is int everywhere); must mirror include/st_hip.h exactly.
-SIGNATURES = {
-    "st_version": [],
-    "st_env_refresh": [],
-    "st_clock_probe": [_c_void_p, _c_void_p, _c_int, _c_int],
-    "st_gemm": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int,
-                _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_uint, _c_int, _c_float, _c_void_p],
-    "st_gemm_stacked": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int,
-                        _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_uint, _c_int,
-                        _c_float, _c_int, _c_long, _c_long],
-    "st_gemm_ws": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p,
-                   _c_int, _c_void_p, _c_uint, _c_int, _c_float, _c_int, _c_long, _c_long],
-    "st_wgrad_group": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                       _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "st_wgrad_wide": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                      _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "st_gemm_ln": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int,
-                   _c_void_p, _c_void_p, _c_float, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p,
-                   _c_void_p, _c_void_p, _c_void_p, _c_uint, _c_int, _c_float, _c_int],
-    "st_wfrag_depth": [],
-    "st_wfrag_build": [_c_void_p, _c_void_p, _c_int],
-    "st_row_chain": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_float, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p,
-                     _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                     _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_uint, _c_int, _c_float, _c_uint, _c_int, _c_float,
-                     _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_ll, _c_float],
-    "st_row_chain_mask_words": [_c_int, _c_int],
-    "st_row_chain512": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_float, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p,
-                        _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                        _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_uint, _c_int, _c_float, _c_uint, _c_int, _c_float,
-                        _c_int, _c_void_p, _c_void_p, _c_int, _c_float],
-    "st_row_chain512_mask_words": [_c_int, _c_int],
-    "st_gemm_kscale": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int,
-                       _c_float],
-    "st_gemm_splitk": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int,
-                       _c_void_p, _c_ll],
-    "st_row_chain_bwd": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
-                         _c_void_p, _c_void_p, _c_void_p, _c_uint, _c_int, _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                         _c_void_p, _c_int, _c_void_p, _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_ll, _c_void_p, _c_ll],
-    "st_zero": [_c_void_p, _c_void_p, _c_ll],
-    "st_row_chain_bwd_colsum_rows": [_c_int, _c_int, _c_int, _c_int],
-    "st_colsum_fold": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p],
-    "st_row_chain512_bwd": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
-                            _c_void_p, _c_void_p, _c_void_p, _c_uint, _c_int, _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                            _c_int, _c_void_p, _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                            _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
-    "st_gemm_lnbwd": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int,
-                      _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p,
-                      _c_void_p, _c_uint, _c_int, _c_float],
-    "st_ln_bwd": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
-                  _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_uint, _c_int, _c_float, _c_float],
-    "st_attn_tile_rows": [_c_int, _c_int, _c_int, _c_int, _c_int],
-    "st_attn_fwd": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p,
-                    _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                    _c_float, _c_void_p, _c_int, _c_void_p, _c_uint, _c_int, _c_float, _c_int],
-    "st_attn_f1_applicable": [_c_int, _c_int, _c_int, _c_int],
-    "st_attn_f1_fwd": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_float, _c_void_p, _c_void_p,
-                       _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int,
-                       _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int,
-                       _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_int, _c_void_p, _c_uint, _c_int, _c_float],
-    "st_attn_sf1_fwd": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_uint, _c_int,
-                        _c_float, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                        _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int,
-                        _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int,
-                        _c_int, _c_float, _c_void_p, _c_int, _c_void_p, _c_uint, _c_int, _c_float],
-    "st_attn_bwd": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
-                    _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
-                    _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                    _c_float, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_uint, _c_int, _c_float, _c_int, _c_void_p, _c_ll],
-    "st_attn_bwd_split_kib": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
-    "st_row_index": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p],
-    "st_pack_rows": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p],
-    "st_ctc_gather": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p],
-    "st_ctc_dlogits": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,
-                       _c_void_p, _c_void_p, _c_void_p, _c_int],
-    "st_attn_probs": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                      _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int],
-    "st_attn_dense_fwd": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,
-                          _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_uint, _c_int, _c_float],
-    "st_attn_dense_bwd": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,
-                          _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                          _c_float, _c_void_p, _c_uint, _c_int, _c_float],
-    "st_feat_stack": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int,
-                      _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int],
-    "st_unpack_rows": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p],
-    "st_pack_grad": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int],
-    "st_embed_pe_fwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
-                        _c_void_p, _c_void_p],
-    "st_embed_bwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int,
-                     _c_void_p, _c_int],
-    "st_cast_bf16": [_c_void_p, _c_void_p, _c_void_p, _c_ll],
-    "st_embed_step": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int],
-    "st_decode_self_attn": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int,
-                            _c_int, _c_float],
-    "st_beam_advance": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p,
-                        _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p,
-                        _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int],
-    "st_ctc_vocab_lp": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p],
-    "st_ctc_prefix_init": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p,
-                           _c_void_p],
-    "st_ctc_prefix_score": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int,
-                            _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "st_beam_pre_beam": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p],
-    "st_beam_advance_joint": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_float, _c_int, _c_int, _c_void_p, _c_int,
-                              _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                              _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int,
-                              _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "st_ctc_best_path": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
-    "st_ctc_loss_ws_kib": [_c_int, _c_int, _c_int],
-    "st_ctc_loss_fwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_ll, _c_void_p],
-    "st_ctc_loss_grad": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_ll,
-                         _c_void_p, _c_void_p, _c_void_p, _c_int],
-    "st_ce_fwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p],
-    "st_ce_bwd": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p,
-                  _c_void_p, _c_int],
-    "st_zero_tails": [_c_void_p, _c_void_p, _c_int],
-    "st_grad_norm_blocks": [],
-    "st_grad_norm": [_c_void_p, _c_void_p, _c_ll, _c_void_p, _c_void_p, _c_void_p, _c_float],
-    "st_cache_reorder": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int],
-    "st_adam_clip": [_c_void_p, _c_ll, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                     _c_float, _c_float, _c_float, _c_float, _c_float],
-    "st_probe_tr16": [_c_void_p, _c_void_p, _c_void_p],
-    "st_probe_mfma": [_c_void_p, _c_void_p, _c_void_p, _c_void_p],
-}
+def parse_header(text: str):
+    """-> (SIGNATURES: name -> argtypes of every ``int st_*(...);`` declaration, ABI version, the ST_EPI_* enum) of the text
+    of include/st_hip.h.  The header's C subset is tiny: a parameter with a ``*`` or of type st_stream_t is a pointer, the five
+    scalar types above are themselves, and ANY other type raises - a new type in the header is a decision, not a default."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    sigs = {}
+    for name, params in re.findall(r"\bint\s+(st_\w+)\s*\(([^)]*)\)\s*;", text):
+        sigs[name] = argtypes = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            words = param.replace("const", " ").split()
+            ctype = ctypes.c_void_p if "*" in param or words[0] == "st_stream_t" else _CTYPES.get(" ".join(words[:-1]))
+            if ctype is None:
+                raise RuntimeError("include/st_hip.h: %s: parameter '%s' has a type the binding does not know" % (name, param.strip()))
+            argtypes.append(ctype)
+    version = re.search(r"#define\s+ST_ABI_VERSION\s+(\d+)", text)
+    epi = {k: int(v) for k, v in re.findall(r"\b(ST_EPI_\w+)\s*=\s*(\d+)", text)}
+    if not sigs or version is None or len(epi) != 8:
+        raise RuntimeError("include/st_hip.h: no declarations / ST_ABI_VERSION / ST_EPI_* found: broken checkout")
+    return sigs, int(version.group(1)), epi
+
+
+def _read_header() -> str:
+    try:
+        with open(_build.ABI_HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise RuntimeError("%s is missing (%s): broken checkout - restore it and rebuild (python __graft_entry__.py)"
+                           % (_build.ABI_HEADER, e)) from None
+
+
+# name -> argtypes (restype is int everywhere), the library's ABI version and st_gemm's epilogue selectors: all read from
+# include/st_hip.h, the one place they are written down
+SIGNATURES, ABI_VERSION, _EPI = parse_header(_read_header())
+(EPI_BF16, EPI_BF16_RELU, EPI_F32, EPI_BF16_MASK, EPI_BF16_ADD, EPI_F32_ATOMIC, EPI_F32_ATOMIC_T, EPI_BF16_DELTA) = (
+    _EPI["ST_" + k] for k in ("EPI_BF16", "EPI_BF16_RELU", "EPI_F32", "EPI_BF16_MASK", "EPI_BF16_ADD", "EPI_F32_ATOMIC",
+                              "EPI_F32_ATOMIC_T", "EPI_BF16_DELTA"))
+_c_int = ctypes.c_int
 
 _LIB = None
 _TIMING = None   # list of (kernel name, tag, algorithmic bytes, start event, end event) while bench.py profiles a step
@@ -227,9 +139,6 @@ def lib_path() -> str:
     return _build.LIB
 
 
-ABI_VERSION = 6      # == ST_ABI_VERSION in include/st_hip.h == st_version() of the library this binding was written against
-
-
 def load(build_if_missing: bool = True):
     """dlopen libst_hip.so (building it first if hipcc is available)."""
     global _LIB
@@ -302,21 +211,85 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-def _mat(t: torch.Tensor, dtype, name: str) -> None:
+# The kernels index these buffers by raw pointer: every property they rely on is checked here, by one of three helpers that
+# RAISE (never `assert`: python -O must not remove them) - RuntimeError for a tensor that is not on the GPU, TypeError /
+# ValueError for a wrong dtype / shape / layout.  Nothing is allocated or formatted on the success path.
+_NO_GPU = "%s must live on the GPU: the HIP path has no CPU fallback"
+
+
+def _mat(t: torch.Tensor, dtype, name: str, rows=None, cols=None, ld=None, min_rows=0) -> None:
+    """A 2-D row matrix with unit column stride; optionally with exactly ``rows`` / at least ``min_rows`` rows, exactly
+    ``cols`` columns and the leading dimension ``ld``."""
     if not t.is_cuda:
-        raise RuntimeError("%s must live on the GPU: the HIP path has no CPU fallback" % name)
+        raise RuntimeError(_NO_GPU % name)
     if t.dtype != dtype:
         raise TypeError("%s: expected %s, got %s" % (name, dtype, t.dtype))
     if t.dim() != 2 or t.stride(1) != 1:
         raise ValueError("%s: expected a 2-D row matrix with unit column stride, got shape %s stride %s"
                          % (name, tuple(t.shape), t.stride()))
+    if ((rows is not None and t.shape[0] != rows) or t.shape[0] < min_rows or (cols is not None and t.shape[1] != cols)
+            or (ld is not None and t.stride(0) != ld)):
+        raise ValueError("%s: shape %s stride %s, expected rows %s (at least %d), columns %s, leading dimension %s (None = any)"
+                         % (name, tuple(t.shape), t.stride(), rows, min_rows, cols, ld))
 
 
 def _vec(t: Optional[torch.Tensor], dtype, n: int, name: str) -> None:
-    if t is None:
+    """None, or a contiguous buffer of at least ``n`` elements read as a flat vector."""
+    if t is None or (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() >= n):
         return
-    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
-        raise ValueError("%s: expected contiguous %s[%d] on the GPU" % (name, dtype, n))
+    if not t.is_cuda:
+        raise RuntimeError(_NO_GPU % name)
+    raise ValueError("%s: expected contiguous %s[>= %d], got %s %s stride %s" % (name, dtype, n, t.dtype, tuple(t.shape), t.stride()))
+
+
+def _dev(t: torch.Tensor, dtype, shape, name: str) -> int:
+    """A contiguous tensor of exactly ``shape`` (an extent of None: any) -> its address."""
+    if t is not None and t.is_cuda and t.dtype == dtype and t.is_contiguous() and (
+            t.shape == shape or (t.dim() == len(shape) and all(w is None or w == n for w, n in zip(shape, t.shape)))):
+        return t.data_ptr()
+    if t is not None and not t.is_cuda:
+        raise RuntimeError(_NO_GPU % name)
+    raise ValueError("%s: expected a contiguous %s %s tensor (None = any extent), got %s" % (
+        name, dtype, list(shape), None if t is None else (t.dtype, tuple(t.shape), t.stride())))
+
+
+# ---- groups of checks that several wrappers share ---------------------------------------------------------------------------------
+def _offsets(q_off, q_len, k_off, k_len) -> int:
+    """The four int32 [B] offset / length vectors of a ragged attention problem -> B."""
+    B = q_off.numel()
+    _vec(q_off, I32, B, "q_off"), _vec(q_len, I32, B, "q_len"), _vec(k_off, I32, B, "k_off"), _vec(k_len, I32, B, "k_len")
+    return B
+
+
+def _ores(ores, O, name="ores") -> None:
+    """``ores`` (optional: what rounding O to bf16 dropped) has its output's shape and stride."""
+    if ores is not None:
+        _mat(ores, BF16, name, rows=O.shape[0], cols=O.shape[1], ld=O.stride(0))
+
+
+def _chain_pre_q(M, d, pre, bq, Qout) -> None:
+    """The PRE stage + query projection that attn_f1_fwd / attn_sf1_fwd run in front of the attention (row_chain's ``pre``)."""
+    R, bo, g0, be0, out0, xhat0, rstd0 = pre
+    _mat(R, BF16, "R", min_rows=M), _mat(out0, BF16, "out0", ld=d), _mat(Qout, BF16, "Qout", rows=M, cols=d)
+    if xhat0 is not None:
+        _mat(xhat0, BF16, "xhat0", ld=d)
+    _vec(bo, F32, d, "bo"), _vec(g0, F32, d, "g0"), _vec(be0, F32, d, "be0"), _vec(bq, F32, d, "bq"), _vec(rstd0, F32, M, "rstd0")
+
+
+def _two_block_stream(chain, who) -> None:
+    if chain.stream.numel() != 8 * (2 * 16 + wfrag_depth()) * 512 or chain.stream.dtype != BF16:
+        raise ValueError("%s: the fragment stream does not match a two-block chain" % who)
+
+
+def _embed_next(embed, n):
+    """beam_advance's ``embed`` = (emb f32 [V', D], pe f32 [P, D], x_next bf16 [n, D]), all contiguous -> the six arguments
+    (emb, V', pe, P, x_next, D) of the C entry points; None -> the launch writes no decoder input."""
+    if embed is None:
+        return None, 0, None, 0, None, 0
+    emb, pe, x_next = embed
+    D = emb.shape[-1]
+    return (_dev(emb, F32, (emb.shape[0], D), "embed: emb"), emb.shape[0], _dev(pe, F32, (pe.shape[0], D), "embed: pe"), pe.shape[0],
+            _dev(x_next, BF16, (n, D), "embed: x_next"), D)
 
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
@@ -483,15 +456,12 @@ def gemm_ln(X, W, bias, res, gamma, beta, out, xhat, rstd, eps=1e-6, relu=False,
     if res is not None:
         _mat(res, BF16, "res")
     if xhat is not None:
-        _mat(xhat, BF16, "xhat")
-        assert xhat.stride(0) == N
+        _mat(xhat, BF16, "xhat", ld=N)
     if pre is not None:
-        _mat(pre, BF16, "pre")
-        assert pre.stride(0) == N
+        _mat(pre, BF16, "pre", ld=N)
     _vec(rstd, F32, M, "rstd")
     if pe is not None:
-        _mat(pe, F32, "pe")
-        assert pe.stride(0) == N
+        _mat(pe, F32, "pe", ld=N)
         _vec(pos, I32, M, "pos")
     _tag("gemm_ln", M, N, K, io=((X, M), W, (res, M), (out, M), (xhat, M), (pre, M), (rstd, M)))
     rc = load().st_gemm_ln(_stream(), X.data_ptr(), X.stride(0), W.data_ptr(), M, N, K, bias.data_ptr(), _p(res),
@@ -517,8 +487,7 @@ def wfrag_build(table):
     """(Re)build weight-fragment streams (csrc/st_rowchain.hip): ``table`` int64 [n_blocks, 4] on the device, one row per
     256 x 256 weight block: (address of its first element, leading dimension | transposed << 32, fragment index inside a
     wave stream | wave stride in fragments << 32, address of the chain's buffer) - see st_amd/chains.py."""
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous() or not table.is_cuda:
-        raise ValueError("wfrag_build: table must be a contiguous int64 [n, 4] device tensor")
+    _dev(table, I64, (None, 4), "wfrag_build: table")
     _tag("wfrag_build", table.shape[0], 0, 0, io=(4.0 * 256 * 256 * table.shape[0],))
     _check(load().st_wfrag_build(_stream(), table.data_ptr(), table.shape[0]), "st_wfrag_build")
 
@@ -558,24 +527,24 @@ def row_chain(A, chain, pre=None, ffn=None, post=None, eps=1e-6, post_kscale=0.0
     d_ff, b1, b2, g1, be1, H, out1, xhat1, rstd1, drop1, drop2 = ffn if ffn else (0,) + z[:10]
     pb, bp, P = post if post else (0, None, None)
     if pre:
-        _mat(R, BF16, "R"), _vec(bo, F32, d, "bo"), _vec(g0, F32, d, "g0"), _vec(be0, F32, d, "be0")
+        _mat(R, BF16, "R", min_rows=M), _vec(bo, F32, d, "bo"), _vec(g0, F32, d, "g0"), _vec(be0, F32, d, "be0")
         if out0 is not None:       # (None: the sublayer's output is only the chain's own running activation - inference)
-            _mat(out0, BF16, "out0")
-            assert out0.stride(0) == d
-        assert (xhat0 is None or xhat0.stride(0) == d) and R.shape[0] >= M
-        assert rstd0 is None or (rstd0.dtype == F32 and rstd0.numel() >= M)
+            _mat(out0, BF16, "out0", ld=d)
+        if xhat0 is not None:
+            _mat(xhat0, BF16, "xhat0", ld=d)
+        _vec(rstd0, F32, M, "rstd0")
     if ffn:
-        _mat(out1, BF16, "out1"), _vec(b1, F32, d_ff, "b1"), _vec(b2, F32, d, "b2")
+        _mat(out1, BF16, "out1", ld=d), _vec(b1, F32, d_ff, "b1"), _vec(b2, F32, d, "b2")
         _vec(g1, F32, d, "g1"), _vec(be1, F32, d, "be1")
         if H is not None:          # (None: inference - the hidden activation stays on the chip)
-            _mat(H, BF16, "H")
-            assert H.stride(0) == d_ff and H.shape == (M, d_ff)
-        assert out1.stride(0) == d and (xhat1 is None or xhat1.stride(0) == d)
-        assert rstd1 is None or (rstd1.dtype == F32 and rstd1.numel() >= M)
-        assert relu_bits is None or (relu_bits.dtype == torch.int64 and relu_bits.is_contiguous() and relu_bits.numel() >= chain_mask_words(M, d_ff, d))
+            _mat(H, BF16, "H", rows=M, cols=d_ff, ld=d_ff)
+        if xhat1 is not None:
+            _mat(xhat1, BF16, "xhat1", ld=d)
+        _vec(rstd1, F32, M, "rstd1")
+        if relu_bits is not None:
+            _vec(relu_bits, I64, chain_mask_words(M, d_ff, d), "relu_bits")
     if post:
-        _mat(P, BF16, "P"), _vec(bp, F32, 256 * pb, "bp")
-        assert P.shape == (M, 256 * pb)
+        _mat(P, BF16, "P", rows=M, cols=256 * pb), _vec(bp, F32, 256 * pb, "bp")
     seed = None
     for dr in (drop1, drop2):
         if dr is not None and dr.thresh:
@@ -584,8 +553,7 @@ def row_chain(A, chain, pre=None, ffn=None, post=None, eps=1e-6, post_kscale=0.0
             seed = dr.seed
     s1, s2 = _drop(drop1), _drop(drop2)
     work = getattr(chain, "split_work", None) if ffn else None
-    if work is not None and not (work.is_cuda and work.is_contiguous() and work.dtype == torch.int32):
-        raise ValueError("row_chain: chain.split_work must be a contiguous int32 tensor on the GPU")
+    _vec(work, I32, 0, "chain.split_work")
     _tag("row_chain", M, n_blocks, d_ff, io=((A, M), (R, M), (out0, M), (xhat0, M), (H, M), relu_bits, (out1, M), (xhat1, M), (P, M),
                                              (rstd0, M), (rstd1, M), 2.0 * 256 * 256 * n_blocks))
     if d == 512:
@@ -609,21 +577,38 @@ def split_work_words() -> int:
     return 256 * 512 * 16 + 256          # 256 workgroups' partials (the launch never uses more) + tickets
 
 
-_splitk_work = {}
+_splitk_work = {}          # device -> the split-K scratch in use
+_ATTN_SPLIT_WORK = {}      # device index -> the attention backward's key-split scratch in use
+_SUPERSEDED = []           # every buffer a larger one has replaced: referenced for the life of the process (see _scratch)
 _SPLITK_BYTES = 4096 + 256 * 65536
+
+
+def _scratch(in_use: dict, key, device, nbytes: int):
+    """Process-wide zero-initialised int32 scratch (tickets + fp32 partials of a last-arriver merge; the kernels leave the
+    tickets zero, launches are stream-ordered, so every launch of one purpose on a device may share it).  -> ``in_use[key]`` if
+    it is large enough; else a larger one takes its place and the old one moves to _SUPERSEDED - it is never freed, because a
+    captured graph may have its address baked into a node.  -> None when the buffer would have to be created inside a
+    stream capture: a tensor born there belongs to that graph's private pool and must never become the process-wide one -
+    the caller decides (splitk_scratch raises, attn_bwd takes a buffer for that one call)."""
+    work = in_use.get(key)
+    if work is None or work.numel() * 4 < nbytes:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        if work is not None:
+            _SUPERSEDED.append(work)
+        work = in_use[key] = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=device)
+    return work
 
 
 def splitk_scratch(device):
     """The per-device scratch of st_gemm_splitk (tickets + 256 fp32 tile partials), zeroed once; the kernel restores its
-    tickets.  TrainStep creates it before a capture (a tensor born inside one belongs to that graph's pool)."""
+    tickets.  TrainStep creates it before a capture."""
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    work = _splitk_work.get(device)
+    work = _scratch(_splitk_work, device, device, _SPLITK_BYTES)
     if work is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("splitk_scratch: first use inside a stream capture; call st_amd.native.splitk_scratch(device) before it")
-        work = _splitk_work[device] = torch.zeros(_SPLITK_BYTES // 4, dtype=torch.int32, device=device)
+        raise RuntimeError("splitk_scratch: first use inside a stream capture; call st_amd.native.splitk_scratch(device) before it")
     return work
 
 
@@ -688,28 +673,26 @@ def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None):
     nb, dP, G, xa, ra, ga, drop, dsa, dga, dba, dbia = head if head else (0,) + z[:10]
     d_ff, bits, msc, dH, xb, rb, gb, dsb, dgb, dbb, dbib = ffn if ffn else (0, None, 1.0) + z[:8]
     O, Ores, dctx, delta = tail if tail else z[:4]
-    d = 512 if (xb is not None and xb.shape[1] == 512) else 256      # (d_model 512: csrc/st_rowchain_pipe512_bwd.cuh - HEAD + FFN + TAIL)
+    wide = next((t for t in (G, xa, xb, O) if t is not None), None)     # whichever d_model-wide operand the call has
+    d = 512 if (wide is not None and wide.shape[1] == 512) else 256     # (d_model 512: csrc/st_rowchain_pipe512_bwd.cuh - HEAD + FFN + TAIL)
     if d == 512:
-        if not (head and ffn and tail) or nb not in (0, 6):
-            raise ValueError("row_chain_bwd (d_model 512): HEAD, FFN and TAIL are required, head blocks 0 or 6")
+        if not (head and ffn and tail) or nb not in (0, 6) or ds_in is not None:
+            raise ValueError("row_chain_bwd (d_model 512): HEAD, FFN and TAIL are required, head blocks 0 or 6, and no ds_in "
+                             "(the chain starts from its HEAD)")
         n_blocks = 2 * nb + 4 * (d_ff // 256) + 4
     else:
         n_blocks = nb + (2 * (d_ff // 256) if ffn else 0) + (1 if tail else 0)
     if n_blocks != chain.n_blocks or chain.stream.numel() != 8 * (n_blocks * 16 + wfrag_depth()) * 512:
         raise ValueError("row_chain_bwd: the fragment stream does not match the chain")
-    for t, cols, name in ((dP, 256 * nb, "dP"), (G, d, "G"), (xa, d, "xhat_a"), (dsa, d, "ds_a"), (ds_in, d, "ds_in"),
-                          (dH, d_ff, "dH"), (xb, d, "xhat_b"), (dsb, d, "ds_b"), (O, d, "O"),
-                          (Ores, d, "Ores"), (dctx, d, "dctx")):
+    for t, cols, ld, name in ((dP, 256 * nb, None, "dP"), (G, d, None, "G"), (xa, d, d, "xhat_a"), (dsa, d, d, "ds_a"),
+                              (ds_in, d, d, "ds_in"), (dH, d_ff, d_ff, "dH"), (xb, d, d, "xhat_b"), (dsb, d, d, "ds_b"),
+                              (O, d, None, "O"), (Ores, d, None if O is None else O.stride(0), "Ores"), (dctx, d, None, "dctx")):
         if t is not None:
-            _mat(t, BF16, name)
-            if t.shape[0] < M or t.shape[1] != cols:
-                raise ValueError("row_chain_bwd: %s has shape %s, expected [>= %d, %d]" % (name, tuple(t.shape), M, cols))
-    for t, name in ((xa, "xhat_a"), (dsa, "ds_a"), (ds_in, "ds_in"), (xb, "xhat_b"), (dsb, "ds_b")):
-        assert t is None or t.stride(0) == d, name
-    assert dH is None or dH.stride(0) == d_ff
-    if ffn and (bits is None or bits.dtype != torch.int64 or not bits.is_contiguous() or bits.numel() < chain_mask_words(M, d_ff, d)):
-        raise ValueError("row_chain_bwd: relu_bits must be the int64 buffer the forward chain wrote (chain_mask_words(M, d_ff) words)")
-    assert O is None or Ores is None or Ores.stride(0) == O.stride(0)
+            _mat(t, BF16, name, min_rows=M, cols=cols, ld=ld)
+    if ffn:
+        if bits is None:
+            raise ValueError("row_chain_bwd: relu_bits must be the int64 buffer the forward chain wrote (chain_mask_words(M, d_ff) words)")
+        _vec(bits, I64, chain_mask_words(M, d_ff, d), "relu_bits")
     for v, n, name in ((ra, M, "rstd_a"), (ga, d, "gamma_a"), (dga, d, "dgamma_a"), (dba, d, "dbeta_a"), (dbia, d, "dbias_a"),
                        (rb, M, "rstd_b"), (gb, d, "gamma_b"), (dgb, d, "dgamma_b"), (dbb, d, "dbeta_b"), (dbib, d, "dbias_b"),
                        (delta, (d // 64) * M, "delta")):
@@ -718,15 +701,14 @@ def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None):
         raise ValueError("row_chain_bwd: without head the chain needs ds_in")
     sd = _drop(drop)
     work = getattr(chain, "split_work", None) if ffn else None
-    if work is not None and not (work.is_cuda and work.is_contiguous() and work.dtype == torch.int32):
-        raise ValueError("row_chain_bwd: chain.split_work must be a contiguous int32 tensor on the GPU")
+    _vec(work, I32, 0, "chain.split_work")
     _tag("row_chain_bwd", M, n_blocks, d_ff, io=((dP, M), (G, M), (xa, M), (dsa, M), (ds_in, M), bits, (dH, M), (xb, M), (dsb, M), (O, M),
                                                  (Ores, M), (dctx, M), (delta, 4 * M), (ra, M), (rb, M), 2.0 * 256 * 256 * n_blocks))
     # encoder-sized HEAD + FFN + TAIL launches leave their LayerNorm column sums in a per-workgroup workspace (no atomics: 251 workgroups
     # adding to the same 768 floats queue for ~8 us per launch); st_colsum_fold adds it to the gradients - at once, or with the deferred
     # weight gradients (flush_colsum_folds)
     ws_rows = 0 if d == 512 else load()._cdll.st_row_chain_bwd_colsum_rows(int(M), int(head is not None), int(d_ff), int(tail is not None))
-    cws = torch.empty(ws_rows * 1536, dtype=F32, device=xb.device) if ws_rows > 0 else None
+    cws = torch.empty(ws_rows * 1536, dtype=F32, device=wide.device) if ws_rows > 0 else None
     if d == 512:
         rc = load().st_row_chain512_bwd(
             _stream(), M, chain.stream.data_ptr(), n_blocks, int(chain.next_blocks), int(nb), _p(dP), 0 if dP is None else dP.stride(0),
@@ -797,12 +779,11 @@ def gemm_lnbwd(dY, W, aux, xhat, rstd, gamma, dx, dgamma=None, dbeta=None, dbias
 
 def ln_bwd(dy, xhat, rstd, gamma, dx, dgamma=None, dbeta=None, dbias=None, mask=None, drop=None, mask_scale=1.0):
     """drop: the forward dropped the LayerNorm output; mask_scale: 1/(1-p) of a dropout between `mask`'s ReLU and the LN."""
-    _mat(dy, BF16, "dy"), _mat(xhat, BF16, "xhat"), _mat(dx, BF16, "dx")
+    _mat(dy, BF16, "dy"), _mat(dx, BF16, "dx")
     M, N = dy.shape
-    assert xhat.stride(0) == N
+    _mat(xhat, BF16, "xhat", ld=N)
     if mask is not None:
-        _mat(mask, BF16, "mask")
-        assert mask.stride(0) == N
+        _mat(mask, BF16, "mask", ld=N)
     _vec(rstd, F32, M, "rstd"), _vec(gamma, F32, N, "gamma")
     _vec(dgamma, F32, N, "dgamma"), _vec(dbeta, F32, N, "dbeta"), _vec(dbias, F32, N, "dbias")
     _tag("ln_bwd", M, N, io=((dy, M), (xhat, M), (dx, M), (mask, M), (rstd, M)))
@@ -836,14 +817,9 @@ def attn_fwd(Q, K, V, O, lse, q_off, q_len, k_off, k_len, n_head, max_q, causal,
     attn_probs of the same sublayer must be told the same."""
     for t, nm in ((Q, "Q"), (K, "K"), (V, "V"), (O, "O")):
         _mat(t, BF16, nm)
-    if ores is not None:
-        _mat(ores, BF16, "ores")
-        if ores.stride(0) != O.stride(0) or ores.shape != O.shape:
-            raise ValueError("attn_fwd: ores must have O's shape and stride")
-    B = q_off.numel()
+    _ores(ores, O)
+    B = _offsets(q_off, q_len, k_off, k_len)
     d_k = Q.shape[1] // n_head
-    for t, nm in ((q_off, "q_off"), (q_len, "q_len"), (k_off, "k_off"), (k_len, "k_len")):
-        _vec(t, I32, B, nm)
     rows = Q.shape[0]
     _vec(lse, F32, n_head * rows, "lse")
     _tag("attn_fwd", n_head, d_k, int(causal), q_len, k_len, io=(Q, K, V, O, ores, lse))
@@ -882,20 +858,12 @@ def attn_f1_fwd(A, chain, pre, post, K, V, O, lse, q_off, q_len, k_off, k_len, n
         row_chain(A, chain, pre=pre, post=post, eps=eps)
         return attn_fwd(Qout, K, V, O, lse, q_off, q_len, k_off, k_len, n_head, max_q, False, scale, work=work, drop=drop,
                         max_k=max_k, ores=ores)
-    for t, nm in ((A, "A"), (R, "R"), (out0, "out0"), (Qout, "Qout"), (K, "K"), (V, "V"), (O, "O")):
+    for t, nm in ((A, "A"), (K, "K"), (V, "V"), (O, "O")):
         _mat(t, BF16, nm)
-    _vec(bo, F32, d, "bo"), _vec(g0, F32, d, "g0"), _vec(be0, F32, d, "be0"), _vec(bq, F32, d, "bq")
-    assert out0.stride(0) == d and (xhat0 is None or xhat0.stride(0) == d) and R.shape[0] >= M and Qout.shape == (M, d)
-    assert rstd0 is None or (rstd0.dtype == F32 and rstd0.numel() >= M)
-    if chain.stream.numel() != 8 * (2 * 16 + wfrag_depth()) * 512 or chain.stream.dtype != BF16:
-        raise ValueError("attn_f1_fwd: the fragment stream does not match a two-block chain")
-    if ores is not None:
-        _mat(ores, BF16, "ores")
-        if ores.stride(0) != O.stride(0) or ores.shape != O.shape:
-            raise ValueError("attn_f1_fwd: ores must have O's shape and stride")
-    B = q_off.numel()
-    for t, nm in ((q_off, "q_off"), (q_len, "q_len"), (k_off, "k_off"), (k_len, "k_len")):
-        _vec(t, I32, B, nm)
+    _chain_pre_q(M, d, pre, bq, Qout)
+    _two_block_stream(chain, "attn_f1_fwd")
+    _ores(ores, O)
+    B = _offsets(q_off, q_len, k_off, k_len)
     _vec(lse, F32, n_head * M, "lse")
     _tag("attn_fwd", n_head, d_k, 0, q_len, k_len, io=(A, R, out0, xhat0, rstd0, Qout, K, V, O, ores, lse))
     rc = load().st_attn_f1_fwd(_stream(), A.data_ptr(), A.stride(0), R.data_ptr(), R.stride(0), chain.stream.data_ptr(), 2,
@@ -928,21 +896,13 @@ def attn_sf1_fwd(qkv, Os, lses, pre, post, chain, K, V, O, lse, q_off, q_len, k_
                  work=work_self, drop=drop_self, max_k=max_q, ores=ores_self)
         return attn_f1_fwd(Os, chain, pre, post, K, V, O, lse, q_off, q_len, k_off, k_len, n_head, max_q, scale, work=work, drop=drop,
                            max_k=max_k, ores=ores, eps=eps)
-    for t, nm in ((qkv, "qkv"), (Os, "Os"), (R, "R"), (out0, "out0"), (Qout, "Qout"), (K, "K"), (V, "V"), (O, "O")):
+    for t, nm in ((qkv, "qkv"), (K, "K"), (V, "V"), (O, "O")):
         _mat(t, BF16, nm)
-    _vec(bo, F32, d, "bo"), _vec(g0, F32, d, "g0"), _vec(be0, F32, d, "be0"), _vec(bq, F32, d, "bq")
-    assert out0.stride(0) == d and (xhat0 is None or xhat0.stride(0) == d) and R.shape[0] >= M and Qout.shape == (M, d) and Os.shape == (M, d)
-    assert rstd0 is None or (rstd0.dtype == F32 and rstd0.numel() >= M)
-    if chain.stream.numel() != 8 * (2 * 16 + wfrag_depth()) * 512 or chain.stream.dtype != BF16:
-        raise ValueError("attn_sf1_fwd: the fragment stream does not match a two-block chain")
-    for o_, r_, nm in ((O, ores, "ores"), (Os, ores_self, "ores_self")):
-        if r_ is not None:
-            _mat(r_, BF16, nm)
-            if r_.stride(0) != o_.stride(0) or r_.shape != o_.shape:
-                raise ValueError("attn_sf1_fwd: %s must have its output's shape and stride" % nm)
-    B = q_off.numel()
-    for t, nm in ((q_off, "q_off"), (q_len, "q_len"), (k_off, "k_off"), (k_len, "k_len")):
-        _vec(t, I32, B, nm)
+    _mat(Os, BF16, "Os", rows=M, cols=d)
+    _chain_pre_q(M, d, pre, bq, Qout)
+    _two_block_stream(chain, "attn_sf1_fwd")
+    _ores(ores, O), _ores(ores_self, Os, "ores_self")
+    B = _offsets(q_off, q_len, k_off, k_len)
     _vec(lse, F32, n_head * M, "lse"), _vec(lses, F32, n_head * M, "lses")
     sd, cd = _drop(drop_self), _drop(drop)
     seed = sd[0] if sd[0] is not None else cd[0]
@@ -967,7 +927,7 @@ def attn_bwd(Q, K, V, O, dO, lse, delta, dQ, dK, dV, q_off, q_len, k_off, k_len,
         _mat(t, BF16, nm)
     if O is not None:      # O = None: delta is an INPUT (produced with dO by gemm(..., epi=EPI_BF16_DELTA)); one launch
         _mat(O, BF16, "O")
-    B = q_off.numel()
+    B = _offsets(q_off, q_len, k_off, k_len)
     d_k = Q.shape[1] // n_head
     rows = Q.shape[0]
     _vec(lse, F32, n_head * rows, "lse"), _vec(delta, F32, n_head * rows, "delta")
@@ -978,7 +938,9 @@ def attn_bwd(Q, K, V, O, dO, lse, delta, dQ, dK, dV, q_off, q_len, k_off, k_len,
         return
     # few queries against many keys (the decoder-encoder attention): scratch for the dQ items' key split across workgroups
     kib = load()._cdll.st_attn_bwd_split_kib(B, n_head, d_k, int(max_q), int(max_k), int(causal)) if (parts == 3 and O is None) else 0
-    swork = _attn_split_work(Q.device, kib) if kib > 0 else None
+    swork = _scratch(_ATTN_SPLIT_WORK, Q.device.index, Q.device, kib * 1024) if kib > 0 else None
+    if kib > 0 and swork is None:      # first use of this size inside a capture: the call's own buffer, from the capturing graph's
+        swork = torch.zeros(kib * 256, dtype=torch.int32, device=Q.device)      # pool, its zero-fill a node of the graph; NOT kept
     _tag("attn_bwd", n_head, d_k, int(causal), q_len, k_len, parts, io=(Q, K, V, O, dO, dQ, dK, dV, lse, delta))
     rc = load().st_attn_bwd(_stream(), Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0),
                             _p(O), 0 if O is None else O.stride(0), dO.data_ptr(), dO.stride(0), lse.data_ptr(),
@@ -991,30 +953,13 @@ def attn_bwd(Q, K, V, O, dO, lse, delta, dQ, dK, dV, q_off, q_len, k_off, k_len,
     _check(rc, "st_attn_bwd")
 
 
-_ATTN_SPLIT_WORK = {}
-
-
-def _attn_split_work(device, kib):
-    """The attention backward's key-split scratch (tickets + fp32 partials), one per device, grown on demand: launches are
-    stream-ordered, the kernel leaves the tickets zero, so every launch may use the same buffer."""
-    key = torch.device(device).index
-    t = _ATTN_SPLIT_WORK.get(key)
-    if t is None or t.numel() * 4 < kib * 1024:
-        t = torch.zeros(kib * 256, dtype=torch.int32, device=device)
-        _ATTN_SPLIT_WORK[key] = t
-    return t
-
-
 def ctc_gather(logits, rowmap, T, cols, lse, lp, V=None):
     """lse[r] = logsumexp(logits[r, :V]); lp[b][t][k] = logits[row(b, t)][cols[b][k]] - lse - see st_ctc_gather."""
-    if not (logits.is_cuda and logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1):
-        raise ValueError("ctc_gather: logits must be an fp32 row matrix on the GPU")
+    _mat(logits, F32, "logits")
     R = logits.shape[0]
     V = logits.shape[1] if V is None else V
     B, C = cols.shape
-    if not (rowmap.dtype == torch.int64 and rowmap.numel() == R and cols.dtype == I32 and cols.is_contiguous()
-            and lp.dtype == F32 and lp.is_contiguous() and tuple(lp.shape) == (B, int(T), C)):
-        raise ValueError("ctc_gather: rowmap i64 [R], cols i32 [B, C], lp f32 [B, T, C] expected")
+    _dev(rowmap, I64, (R,), "ctc_gather: rowmap"), _dev(cols, I32, (B, C), "ctc_gather: cols"), _dev(lp, F32, (B, int(T), C), "ctc_gather: lp")
     _vec(lse, F32, R, "lse")
     _tag("ctc_gather", R, V, C, io=(4.0 * R * V, 4.0 * R * C))
     _check(load().st_ctc_gather(_stream(), logits.data_ptr(), logits.stride(0), R, V, rowmap.data_ptr(), int(T), cols.data_ptr(), C,
@@ -1026,12 +971,10 @@ def ctc_dlogits(logits, lse, rowmap, T, roww, scat, gsmall, grad_out, dlogits, V
     R = logits.shape[0]
     V = logits.shape[1] if V is None else V
     B, C = scat.shape
-    _mat(dlogits, BF16, "dlogits")
-    if dlogits.shape[0] != R or dlogits.shape[1] < V or dlogits.stride(0) % 8 or dlogits.shape[1] != dlogits.stride(0):
+    _mat(dlogits, BF16, "dlogits", rows=R, ld=dlogits.shape[-1])
+    if dlogits.shape[1] < V or dlogits.stride(0) % 8:
         raise ValueError("ctc_dlogits: dlogits must be a contiguous bf16 [R, >= V] matrix with a row length that is a multiple of 8")
-    if not (scat.dtype == I32 and scat.is_contiguous() and gsmall.dtype == F32 and gsmall.is_contiguous()
-            and tuple(gsmall.shape) == (B, int(T), C) and roww.dtype == F32 and roww.numel() == B):
-        raise ValueError("ctc_dlogits: scat i32 [B, C], gsmall f32 [B, T, C], roww f32 [B] expected")
+    _dev(scat, I32, (B, C), "ctc_dlogits: scat"), _dev(gsmall, F32, (B, int(T), C), "ctc_dlogits: gsmall"), _dev(roww, F32, (B,), "ctc_dlogits: roww")
     _vec(grad_out, F32, 1, "grad_out")
     _tag("ctc_dlogits", R, V, C, io=(4.0 * R * V, 2.0 * R * dlogits.shape[1]))
     _check(load().st_ctc_dlogits(_stream(), logits.data_ptr(), logits.stride(0), R, V, lse.data_ptr(), rowmap.data_ptr(), int(T),
@@ -1131,8 +1074,8 @@ def attn_dense_fwd(Q, K, V, mask, O, lse, B, n_head, Lq, Lk, scale, drop=None, w
     for t, nm in ((Q, "Q"), (K, "K"), (V, "V"), (O, "O")):
         _mat(t, BF16, nm)
     d_k = Q.shape[1] // n_head
-    if mask is not None and not (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (B, Lq, Lk)):
-        raise ValueError("attn_dense_fwd: mask must be a contiguous uint8 [B, Lq, Lk] tensor on the GPU")
+    if mask is not None:
+        _dev(mask, torch.uint8, (B, Lq, Lk), "attn_dense_fwd: mask")
     if Q.shape[0] != B * Lq or K.shape[0] != B * Lk or V.shape[0] != B * Lk:
         raise ValueError("attn_dense_fwd: padded layouts expected (B Lq query rows, B Lk key rows)")
     _vec(lse, F32, n_head * B * Lq, "lse")
@@ -1160,14 +1103,12 @@ def attn_dense_bwd(Q, K, V, mask, dO, lse, delta, dQ, dK, dV, B, n_head, Lq, Lk,
 
 def feat_stack(x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out):
     """Raw padded features x fp32 [B, T, F] -> stacked / subsampled / normalised bf16 rows (Dataset.py front-end)."""
-    if not (x.is_cuda and x.dtype == F32 and x.is_contiguous() and x.dim() == 3):
-        raise ValueError("feat_stack: x must be a contiguous fp32 [B, T, F] tensor on the GPU")
+    _dev(x, F32, (None, None, None), "feat_stack: x")
     B, T, F = x.shape
     _vec(in_len, I32, B, "in_len"), _vec(out_off, I32, B, "out_off"), _vec(out_len, I32, B, "out_len")
     _mat(out, BF16, "out")
-    if stats is not None and not (stats.is_cuda and stats.dtype == F32 and stats.is_contiguous()
-                                  and tuple(stats.shape) == (B, 2, F + 1)):
-        raise ValueError("feat_stack: stats must be fp32 [B, 2, F+1] on the GPU")
+    if stats is not None:
+        _dev(stats, F32, (B, 2, F + 1), "feat_stack: stats")
     _tag("feat_stack", B, T, F)
     rc = load().st_feat_stack(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), int(left), int(right),
                               int(interval), out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(),
@@ -1185,11 +1126,9 @@ def row_index(off, length, max_len, row_pos, row_seq=None):
 
 
 def pack_rows(x, off, length, out):
-    if not (x.is_cuda and x.dtype == F32 and x.is_contiguous() and x.dim() == 3):
-        raise ValueError("pack_rows: x must be a contiguous fp32 [B, T, F] GPU tensor")
+    _dev(x, F32, (None, None, None), "pack_rows: x")
     B, T, Fd = x.shape
-    _mat(out, BF16, "out")
-    assert out.stride(0) == Fd
+    _mat(out, BF16, "out", ld=Fd)
     _tag("pack_rows", out.shape[0], Fd, io=(float(out.shape[0]) * Fd * x.element_size(), out))
     _check(load().st_pack_rows(_stream(), x.data_ptr(), B, T, Fd, off.data_ptr(), length.data_ptr(), out.data_ptr()),
            "st_pack_rows")
@@ -1198,15 +1137,15 @@ def pack_rows(x, off, length, out):
 
 def unpack_rows(x, off, length, out):
     _mat(x, BF16, "x")
+    _dev(out, F32, (None, None, None), "unpack_rows: out")
     B, T, D = out.shape
-    assert out.dtype == F32 and out.is_contiguous() and out.is_cuda
     _check(load().st_unpack_rows(_stream(), x.data_ptr(), x.stride(0), B, T, D, off.data_ptr(), length.data_ptr(),
                                  out.data_ptr()), "st_unpack_rows")
     return out
 
 
 def pack_grad(g, off, length, out):
-    assert g.is_cuda and g.dtype == F32 and g.is_contiguous() and g.dim() == 3
+    _dev(g, F32, (None, None, None), "pack_grad: g")
     B, T, D = g.shape
     _mat(out, BF16, "out")
     _check(load().st_pack_grad(_stream(), g.data_ptr(), B, T, D, off.data_ptr(), length.data_ptr(), out.data_ptr(),
@@ -1215,11 +1154,10 @@ def pack_grad(g, off, length, out):
 
 
 def embed_pe_fwd(tok, emb, pe, off, length, out):
-    assert tok.is_cuda and tok.dtype == I64 and tok.is_contiguous() and tok.dim() == 2
+    _dev(tok, I64, (None, None), "embed_pe_fwd: tok")
     B, L = tok.shape
-    _mat(emb, F32, "emb"), _mat(pe, F32, "pe"), _mat(out, BF16, "out")
-    D = emb.shape[1]
-    assert emb.stride(0) == D and pe.stride(0) == D and out.stride(0) == D and pe.shape[0] >= L
+    D = emb.shape[-1]
+    _mat(emb, F32, "emb", ld=D), _mat(pe, F32, "pe", ld=D, min_rows=L), _mat(out, BF16, "out", ld=D)
     _tag("embed_pe_fwd", out.shape[0], D, io=(8.0 * out.shape[0] * D, out))
     _check(load().st_embed_pe_fwd(_stream(), tok.data_ptr(), B, L, emb.data_ptr(), emb.shape[0], pe.data_ptr(), D,
                                   off.data_ptr(), length.data_ptr(), out.data_ptr()), "st_embed_pe_fwd")
@@ -1227,11 +1165,10 @@ def embed_pe_fwd(tok, emb, pe, off, length, out):
 
 
 def embed_bwd(tok, dy, off, length, pad_idx, demb):
-    assert tok.is_cuda and tok.dtype == I64 and tok.is_contiguous()
+    _dev(tok, I64, (None, None), "embed_bwd: tok")
     B, L = tok.shape
-    _mat(dy, BF16, "dy"), _mat(demb, F32, "demb")
+    _mat(dy, BF16, "dy"), _mat(demb, F32, "demb", ld=demb.shape[-1])
     D = demb.shape[1]
-    assert demb.stride(0) == D
     _tag("embed_bwd", dy.shape[0], D, io=(dy, 8.0 * dy.shape[0] * D))
     _check(load().st_embed_bwd(_stream(), tok.data_ptr(), B, L, dy.data_ptr(), dy.stride(0), D, off.data_ptr(),
                                length.data_ptr(), int(pad_idx), demb.data_ptr(), demb.shape[0]), "st_embed_bwd")
@@ -1241,19 +1178,11 @@ def embed_bwd(tok, dy, off, length, pad_idx, demb):
 def embed_step(tokens, emb, pe, step, out):
     """out bf16 [n, D] = emb[tokens] + pe[step] (step: i64 [1] on the device) - one beam-search step's decoder input."""
     n, D = out.shape
-    _mat(out, BF16, "out"), _vec(tokens, I64, n, "tokens"), _vec(step, I64, 1, "step")
-    if not (emb.is_cuda and emb.dtype == F32 and emb.dim() == 2 and emb.is_contiguous() and emb.shape[1] == D and
-            pe.is_cuda and pe.dtype == F32 and pe.dim() == 2 and pe.is_contiguous() and pe.shape[1] == D and out.stride(0) == D):
-        raise ValueError("embed_step: emb [V, D] / pe [S, D] contiguous fp32, out contiguous [n, D]")
+    _mat(out, BF16, "out", ld=D), _vec(tokens, I64, n, "tokens"), _vec(step, I64, 1, "step")
+    _dev(emb, F32, (emb.shape[0], D), "embed_step: emb"), _dev(pe, F32, (pe.shape[0], D), "embed_step: pe")
     _check(load().st_embed_step(_stream(), tokens.data_ptr(), emb.data_ptr(), emb.shape[0], pe.data_ptr(), step.data_ptr(),
                                 out.data_ptr(), n, D), "st_embed_step")
     return out
-
-
-def _lineage(anc, n, S, name):
-    if anc is not None and not (anc.is_cuda and anc.dtype == I32 and anc.is_contiguous() and tuple(anc.shape) == (n, S)):
-        raise ValueError("%s: anc must be a contiguous int32 [n, S] tensor on the GPU" % name)
-    return anc.data_ptr() if anc is not None else None
 
 
 def decode_self_attn(qkv, cache, step, ctx, n_head, scale, anc=None):
@@ -1264,14 +1193,15 @@ def decode_self_attn(qkv, cache, step, ctx, n_head, scale, anc=None):
     _mat(qkv, BF16, "qkv"), _mat(ctx, BF16, "ctx")
     n, S, w = cache.shape
     d = w // 2
-    if not (cache.is_cuda and cache.dtype == BF16 and cache.is_contiguous()) or qkv.shape != (n, 3 * d) or ctx.shape != (n, d):
+    _dev(cache, BF16, (n, S, w), "decode_self_attn: cache")
+    if qkv.shape != (n, 3 * d) or ctx.shape != (n, d):
         raise ValueError("decode_self_attn: qkv [n, 3d], cache [n, S, 2d] (contiguous bf16), ctx [n, d]")
     if d % n_head or d // n_head != 64 or S > 128:
         raise ValueError("decode_self_attn: head width 64 and at most 128 cached positions")
     _vec(step, I64, 1, "step")
     _tag("decode_self_attn", n, n_head, S)
     _check(load().st_decode_self_attn(_stream(), qkv.data_ptr(), qkv.stride(0), cache.data_ptr(), step.data_ptr(),
-                                      _lineage(anc, n, S, "decode_self_attn"), ctx.data_ptr(), ctx.stride(0), n, S, int(n_head),
+                                      None if anc is None else _dev(anc, I32, (n, S), "decode_self_attn: anc"), ctx.data_ptr(), ctx.stride(0), n, S, int(n_head),
                                       d // n_head, float(scale)), "st_decode_self_attn")
 
 
@@ -1286,37 +1216,24 @@ def beam_advance(logits, V, beam, step, eos, scores, tokens, done, lengths, hist
     ``embed`` = (emb f32 [V', D], pe f32 [P, D], x_next bf16 [B * beam, D]): the launch also writes the next step's decoder
     input for the chosen tokens (embed_step's arithmetic at position step + 1; needs ``work``)."""
     B = scores.shape[0]
-    if not (logits.is_cuda and logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == B * beam):
-        raise ValueError("beam_advance: logits must be an fp32 [B * beam, >= V] row matrix on the GPU")
+    _mat(logits, F32, "logits", rows=B * beam)
     for t, dt, n, name in ((scores, F32, B * beam, "scores"), (tokens, I64, B * beam, "tokens"), (lengths, I64, B, "lengths"),
                            (order, I64, B * beam, "order"), (step, I64, 1, "step")):
         _vec(t, dt, n, name)
-    if done.dtype != torch.bool or not done.is_contiguous() or done.numel() != B or not done.is_cuda:
-        raise ValueError("beam_advance: done must be a contiguous bool [B] tensor on the GPU")
+    _dev(done, torch.bool, (B,), "done")
     S = hist_scores.shape[0]
     for t, dt, name in ((hist_scores, F32, "hist_scores"), (back, I64, "back"), (toks, I64, "toks")):
-        if tuple(t.shape) != (S, B, beam) or t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("beam_advance: %s must be a contiguous [S, B, beam] tensor" % name)
-    if work is not None and not (work.is_cuda and work.dtype == I64 and work.is_contiguous() and work.numel() >= beam_work_words(B, beam)):
-        raise ValueError("beam_advance: work must be a contiguous int64 tensor of >= beam_work_words(B, beam) elements on the GPU")
+        _dev(t, dt, (S, B, beam), name)
+    _vec(work, I64, beam_work_words(B, beam), "work")
     if (advance_step or embed is not None) and work is None:
         raise ValueError("beam_advance: advance_step / embed need the work buffer")
-    emb = pe = x_next = None
-    if embed is not None:
-        emb, pe, x_next = embed
-        if not (emb.is_cuda and emb.dtype == F32 and emb.is_contiguous() and pe.is_cuda and pe.dtype == F32 and pe.is_contiguous()
-                and emb.dim() == 2 and pe.dim() == 2 and emb.shape[1] == pe.shape[1] and x_next.is_cuda and x_next.dtype == BF16
-                and x_next.is_contiguous() and tuple(x_next.shape) == (B * beam, emb.shape[1])):
-            raise ValueError("beam_advance: embed = (emb f32 [V', D], pe f32 [P, D], x_next bf16 [B * beam, D]), contiguous, on the GPU")
     _tag("beam_advance", B, beam, V)
     _check(load().st_beam_advance(_stream(), logits.data_ptr(), logits.stride(0), int(V), int(beam), B, step.data_ptr(), int(eos),
                                   scores.data_ptr(), tokens.data_ptr(), done.data_ptr(), lengths.data_ptr(),
                                   hist_scores.data_ptr(), back.data_ptr(), toks.data_ptr(), order.data_ptr(),
-                                  work.data_ptr() if work is not None else None,
-                                  _lineage(anc, B * beam, anc.shape[1] if anc is not None and anc.dim() == 2 else 0, "beam_advance"),
-                                  int(anc.shape[1]) if anc is not None else 0,
-                                  step.data_ptr() if advance_step else None, _p(emb), 0 if emb is None else emb.shape[0], _p(pe),
-                                  0 if pe is None else pe.shape[0], _p(x_next), 0 if emb is None else emb.shape[1]), "st_beam_advance")
+                                  _p(work), None if anc is None else _dev(anc, I32, (B * beam, anc.shape[-1]), "anc"),
+                                  0 if anc is None else anc.shape[1], step.data_ptr() if advance_step else None,
+                                  *_embed_next(embed, B * beam)), "st_beam_advance")
 
 
 def beam_work_words(B: int, beam: int) -> int:
@@ -1326,12 +1243,6 @@ def beam_work_words(B: int, beam: int) -> int:
 
 
 # ---- joint CTC / attention beam search (csrc/st_ctc_decode.hip) ---------------------------------------------------------------
-def _dev(t, dtype, shape, name):
-    if t is None or not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
-        raise ValueError("%s: expected a contiguous %s %s tensor on the GPU" % (name, dtype, list(shape)))
-    return t.data_ptr()
-
-
 def ctc_vocab_lp(logits, V, off, length, T_cap, lse, lpT):
     """CTC logits f32 [R, >= V] (packed encoder rows, utterance b at off[b] .. off[b] + len[b]) -> lse f32 [R] and the
     vocabulary-major log-probabilities lpT f32 [B, V, T_cap] (frames past len[b]: 0) - see st_ctc_vocab_lp."""
@@ -1406,13 +1317,6 @@ def beam_advance_joint(ids, lp, delta, ctc_weight, beam, step, eos, scores, toke
         raise ValueError("beam_advance_joint: advance_step needs the ticket word")
     if ticket is not None:
         _vec(ticket, I64, 1, "ticket")
-    emb = pe = x_next = None
-    if embed is not None:
-        emb, pe, x_next = embed
-        if not (emb.is_cuda and emb.dtype == F32 and emb.is_contiguous() and pe.is_cuda and pe.dtype == F32 and pe.is_contiguous()
-                and emb.dim() == 2 and pe.dim() == 2 and emb.shape[1] == pe.shape[1] and x_next.is_cuda and x_next.dtype == BF16
-                and x_next.is_contiguous() and tuple(x_next.shape) == (B * beam, emb.shape[1])):
-            raise ValueError("beam_advance_joint: embed = (emb f32 [V', D], pe f32 [P, D], x_next bf16 [B * beam, D]), contiguous")
     T_cap, cp = 0, [None] * 6
     if ctc is not None:
         cand_gam, cand_psi, gam, psi, last, frozen = ctc
@@ -1425,11 +1329,9 @@ def beam_advance_joint(ids, lp, delta, ctc_weight, beam, step, eos, scores, toke
     _check(load().st_beam_advance_joint(_stream(), ids.data_ptr(), lp.data_ptr(), delta.data_ptr(), K, float(ctc_weight), int(beam), B,
                                         step.data_ptr(), int(eos), scores.data_ptr(), tokens.data_ptr(), done.data_ptr(),
                                         lengths.data_ptr(), hist_scores.data_ptr(), back.data_ptr(), toks.data_ptr(), order.data_ptr(),
-                                        _lineage(anc, B * beam, anc.shape[1] if anc is not None and anc.dim() == 2 else 0,
-                                                 "beam_advance_joint"),
-                                        int(anc.shape[1]) if anc is not None else 0, step.data_ptr() if advance_step else None,
-                                        _p(ticket), _p(emb), 0 if emb is None else emb.shape[0], _p(pe), 0 if pe is None else pe.shape[0],
-                                        _p(x_next), 0 if emb is None else emb.shape[1], int(T_cap), *cp), "st_beam_advance_joint")
+                                        None if anc is None else _dev(anc, I32, (B * beam, anc.shape[-1]), "anc"),
+                                        0 if anc is None else anc.shape[1], step.data_ptr() if advance_step else None,
+                                        _p(ticket), *_embed_next(embed, B * beam), int(T_cap), *cp), "st_beam_advance_joint")
 
 
 def ctc_best_path(logits, V, out):
@@ -1444,8 +1346,7 @@ def ctc_best_path(logits, V, out):
 def cache_reorder(cache, order, step, beam):
     """cache bf16 [L, n, S, W] (contiguous): rows of every utterance re-gathered by ``order`` (int64 [n], device) for the
     positions <= step (int64 [1], device) - see st_cache_reorder."""
-    if not (cache.is_cuda and cache.dtype == BF16 and cache.is_contiguous() and cache.dim() == 4):
-        raise ValueError("cache_reorder: cache must be a contiguous bf16 [L, n, S, W] tensor on the GPU")
+    _dev(cache, BF16, (None, None, None, None), "cache_reorder: cache")
     L, n, S, W = cache.shape
     _vec(order, I64, n, "order"), _vec(step, I64, 1, "step")
     _check(load().st_cache_reorder(_stream(), cache.data_ptr(), order.data_ptr(), step.data_ptr(), L, n, S, W, int(beam)),
@@ -1453,24 +1354,13 @@ def cache_reorder(cache, order, step, beam):
     return cache
 
 
-def _ce_target(target, index, R, who):
-    """target i64 [R], or any i64 vector addressed through index (i64 [R])."""
-    if index is None:
-        _vec(target, I64, R, "target")
-    else:
-        _vec(index, I64, R, "target_index")
-        if not (target.is_cuda and target.dtype == I64 and target.is_contiguous()):
-            raise ValueError("%s: target must be a contiguous int64 tensor on the GPU" % who)
-
-
 def ce_fwd(logits, target, ignore_index, lse, sums, V=None, index=None):
     """lse[r] = logsumexp(logits[r, :V]); sums = (sum of the non-ignored rows' losses, their count, the mean = the loss)
     - see st_ce_fwd.  index: row r's target is target.view(-1)[index[r]]."""
-    if not (logits.is_cuda and logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1):
-        raise ValueError("ce_fwd: logits must be an fp32 row matrix on the GPU")
+    _mat(logits, F32, "logits")
     R = logits.shape[0]
     V = logits.shape[1] if V is None else V
-    _ce_target(target, index, R, "ce_fwd")
+    _vec(target, I64, R if index is None else 0, "target"), _vec(index, I64, R, "target_index")      # (with index: any i64 vector)
     _vec(lse, F32, R, "lse"), _vec(sums, F32, 3, "sums")
     row_loss = torch.empty(R, dtype=F32, device=logits.device)       # scratch: summed by the call's second launch
     _tag("ce_fwd", R, V, 0, io=(2.0 * R * V, 8.0 * R))
@@ -1482,10 +1372,10 @@ def ce_bwd(logits, target, ignore_index, lse, sums, grad_out, dlogits, V=None, i
     """dlogits (bf16, same shape as logits) = d(mean loss) / d(logits) * grad_out - see st_ce_bwd."""
     R = logits.shape[0]
     V = logits.shape[1] if V is None else V
-    _mat(dlogits, BF16, "dlogits")
-    if dlogits.shape[0] != R or dlogits.shape[1] < V or dlogits.stride(0) % 8 or dlogits.shape[1] != dlogits.stride(0):
+    _mat(dlogits, BF16, "dlogits", rows=R, ld=dlogits.shape[-1])
+    if dlogits.shape[1] < V or dlogits.stride(0) % 8:
         raise ValueError("ce_bwd: dlogits must be a contiguous bf16 [R, >= V] matrix with a row length that is a multiple of 8")
-    _ce_target(target, index, R, "ce_bwd")
+    _vec(target, I64, R if index is None else 0, "target"), _vec(index, I64, R, "target_index")
     _vec(grad_out, F32, 1, "grad_out")
     _tag("ce_bwd", R, V, 0, io=(4.0 * R * V, 8.0 * R))
     _check(load().st_ce_bwd(_stream(), logits.data_ptr(), logits.stride(0), R, V, target.data_ptr(), _p(index), int(ignore_index),
@@ -1496,8 +1386,7 @@ def ce_bwd(logits, target, ignore_index, lse, sums, grad_out, dlogits, V=None, i
 def zero_tails(table, n_max):
     """table: int64 device tensor [n_max * 4] of (address, bytes per row, capacity rows, address of the valid-row count) - see
     st_zero_tails."""
-    if not (table.is_cuda and table.dtype == I64 and table.is_contiguous() and table.numel() >= 4 * n_max):
-        raise ValueError("zero_tails: table must be a contiguous int64 GPU tensor of 4 * n_max elements")
+    _vec(table, I64, 4 * n_max, "zero_tails: table")
     _tag("zero_tails", n_max)
     _check(load().st_zero_tails(_stream(), table.data_ptr(), int(n_max)), "st_zero_tails")
 
@@ -1531,8 +1420,9 @@ def grad_norm_scratch(device):
 def grad_norm(g, scratch, out, step=None, grad_scale=1.0):
     """out (fp32 scalar tensor) = grad_scale * ||g||_2 over the flat fp32 buffer g; step (fp32 scalar tensor, optional) += 1 -
     see st_grad_norm."""
-    if not (g.is_cuda and g.dtype == F32 and g.is_contiguous() and g.numel() % 4 == 0):
-        raise ValueError("grad_norm: g must be a contiguous fp32 GPU buffer of a multiple of 4 elements")
+    _vec(g, F32, 0, "grad_norm: g")
+    if g.numel() % 4:
+        raise ValueError("grad_norm: g must hold a multiple of 4 elements")
     _vec(scratch, F32, _norm_blocks() + 1, "scratch")
     for t, nm in ((out, "out"), (step, "step")):
         if t is not None and not (t.is_cuda and t.dtype == F32 and t.numel() == 1):
@@ -1544,8 +1434,9 @@ def grad_norm(g, scratch, out, step=None, grad_scale=1.0):
 
 
 def cast_bf16(src, dst):
-    assert src.is_cuda and dst.is_cuda and src.dtype == F32 and dst.dtype == BF16
-    assert src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()
+    _vec(src, F32, 0, "cast_bf16: src"), _vec(dst, BF16, src.numel(), "cast_bf16: dst")
+    if dst.numel() != src.numel():
+        raise ValueError("cast_bf16: dst holds %d elements, src %d" % (dst.numel(), src.numel()))
     _tag("cast_bf16", src.numel(), io=(src, dst))
     _check(load().st_cast_bf16(_stream(), src.data_ptr(), dst.data_ptr(), src.numel()), "st_cast_bf16")
     return dst
@@ -1555,10 +1446,11 @@ def adam_clip(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_sca
     """In place: g *= grad_scale * min(1, max_norm / (gnorm + 1e-6)); (p, m, v) <- Adam(p, g, m, v; lr, step).  lr / step /
     gnorm are 0-dim fp32 device tensors (gnorm None: no clipping); grad_scale: see st_adam_clip (1 / world behind a summing
     all-reduce)."""
-    for t in (p, g, m, v):
-        assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == p.numel()
-    for t in (lr, step) + ((gnorm,) if gnorm is not None else ()):
-        assert t.is_cuda and t.dtype == F32 and t.numel() == 1
+    n = p.numel()
+    for t, k, nm in ((p, n, "p"), (g, n, "g"), (m, n, "m"), (v, n, "v"), (lr, 1, "lr"), (step, 1, "step"), (gnorm, 1, "gnorm")):
+        _vec(t, F32, k, nm)
+        if t is not None and t.numel() != k:
+            raise ValueError("adam_clip: %s holds %d elements, expected %d" % (nm, t.numel(), k))
     _tag("adam_clip", p.numel(), io=(32.0 * p.numel(),))      # p, g, m, v read; p, m, v written; g zeroed (fp32)
     _check(load().st_adam_clip(_stream(), p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(),
                                step.data_ptr(), _p(gnorm), float(max_norm), float(beta1), float(beta2), float(eps),

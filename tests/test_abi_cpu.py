@@ -1,11 +1,19 @@
 """-m "not gpu": the C-ABI library builds, loads, and exports exactly the entry
-points include/st_hip.h declares (no compute calls - there is no GPU here)."""
+points include/st_hip.h declares (no compute calls - there is no GPU here); the header is the one copy of the ABI - the
+sources are compiled against it and the binding is parsed from it."""
+import ctypes
 import os
 import re
+import shutil
+import subprocess
 
-from st_amd import native
+import pytest
+
+from st_amd import build, native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "st_hip.h")
+DEV_HOOKS = {"st_dev_chain_trace"}        # development entry points: defined in csrc/, deliberately not in the header or the binding
 
 
 def _header_functions():
@@ -23,17 +31,117 @@ def test_library_exports_header_symbols():
     assert lib.st_version() == native.ABI_VERSION
 
 
-def test_header_argument_counts_match_binding():
-    text = open(os.path.join(ROOT, "include", "st_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name, args in re.findall(r"\bint\s+(st_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", text, flags=re.S):
+def _source(name):
+    with open(os.path.join(build.CSRC, name)) as f:
+        return f.read()
+
+
+def test_sources_define_exactly_the_declared_entry_points():
+    """Every `extern "C" int st_*` of the library's sources is a declaration of the header (65 today) or a development hook -
+    and nothing the header declares is left undefined."""
+    found = set()
+    for src in build.SOURCES:
+        found |= set(re.findall(r'extern\s+"C"\s+int\s+(st_\w+)\s*\(', _source(src)))
+    declared = _header_functions()
+    assert len(declared) == 65
+    assert found == declared | DEV_HOOKS, (found ^ (declared | DEV_HOOKS))
+
+
+def test_every_source_is_compiled_against_the_header():
+    """st_hip.h reaches every translation unit - directly, or through a header the file demonstrably includes - so a definition
+    that disagrees with its declaration stops the build."""
+    def includes(name, seen):
+        if name in seen:
+            return False
+        seen.add(name)
+        local = re.findall(r'^\s*#\s*include\s+"([^"]+)"', _source(name), flags=re.M)
+        return "st_hip.h" in local or any(os.path.exists(os.path.join(build.CSRC, h)) and includes(h, seen) for h in local)
+    for src in build.SOURCES:
+        assert includes(src, set()), "%s does not include st_hip.h" % src
+    assert any(f == "-I" + os.path.relpath(os.path.dirname(HEADER), build.CSRC) for f in build.FLAGS)
+    assert os.path.samefile(build.ABI_HEADER, HEADER)
+
+
+def test_header_edits_rebuild(monkeypatch, tmp_path):
+    """The header's bytes are part of the library's source hash and of every object's cache key."""
+    other = tmp_path / "st_hip.h"
+    other.write_bytes(open(HEADER, "rb").read() + b"/* edited */\n")
+    before = build.source_hash(), build._headers()
+    monkeypatch.setattr(build, "ABI_HEADER", str(other))
+    assert build.source_hash() != before[0] and build._headers() != before[1]
+
+
+def test_width_sensitive_slots_of_the_parsed_binding():
+    """Pinned literally, so a parser bug cannot hide behind "derived from the header": an int where a long long belongs shifts or
+    truncates the arguments of kernels that see raw pointers."""
+    S = native.SIGNATURES
+    for name, args in re.findall(r"\bint\s+(st_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S),
+                                 flags=re.S):
         n = 0 if args.strip() == "void" else args.count(",") + 1
-        assert n == len(native.SIGNATURES[name]), (name, n, len(native.SIGNATURES[name]))
+        assert n == len(S[name]), (name, n, len(S[name]))
+    assert S["st_gemm_splitk"][-1] is ctypes.c_longlong and S["st_gemm_splitk"][-2] is ctypes.c_void_p
+    assert S["st_gemm_stacked"][-2:] == [ctypes.c_long, ctypes.c_long] and S["st_gemm_stacked"][-3] is ctypes.c_int
+    assert S["st_gemm_ws"][-2:] == [ctypes.c_long, ctypes.c_long]
+    assert S["st_gemm"][18] is ctypes.c_uint and S["st_gemm"][20] is ctypes.c_float and S["st_gemm"][19] is ctypes.c_int
+    assert S["st_gemm"][0] is ctypes.c_void_p and S["st_gemm"][17] is ctypes.c_void_p and len(S["st_gemm"]) == 22
+    assert S["st_zero"] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong]
+    assert S["st_version"] == [] and len(S["st_version"]) == 0 and S["st_wfrag_depth"] == []
+    assert S["st_adam_clip"][1] is ctypes.c_longlong and S["st_adam_clip"][-5:] == [ctypes.c_float] * 5
+    assert S["st_row_chain"][-2] is ctypes.c_longlong and S["st_row_chain"][-1] is ctypes.c_float
+    assert S["st_row_chain"][22] is ctypes.c_void_p          # unsigned long long* relu_bits: a pointer, not a scalar
+    assert S["st_attn_bwd"][-1] is ctypes.c_longlong and S["st_ctc_loss_fwd"][-2] is ctypes.c_longlong
+    assert S["st_beam_advance_joint"][5] is ctypes.c_float
+
+
+@pytest.mark.parametrize("decl,param", [("int st_a(st_stream_t stream, double x);", "double x"),
+                                        ("int st_b(const void* p, size_t n);", "size_t n"),
+                                        ("int st_c(int k, struct st_opts opts);", "struct st_opts opts"),
+                                        ("int st_d(unsigned long long words);", "unsigned long long words")])
+def test_parser_refuses_a_type_it_does_not_know(decl, param):
+    text = "#define ST_ABI_VERSION 6\nenum { %s };\n%s\n" % (", ".join("ST_EPI_%d = %d" % (i, i) for i in range(8)), decl)
+    with pytest.raises(RuntimeError) as e:
+        native.parse_header(text)
+    assert param in str(e.value) and decl[4:8] in str(e.value)
+    ok = text.replace(param, "long long n")
+    sigs, version, epi = native.parse_header(ok)
+    assert sigs[decl[4:8]][-1] is ctypes.c_longlong and version == 6 and len(epi) == 8
+
+
+def test_version_and_epilogues_come_from_the_header():
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert native.ABI_VERSION == int(re.search(r"#define\s+ST_ABI_VERSION\s+(\d+)", text).group(1)) == native.load().st_version()
+    enum = dict(re.findall(r"\bST_(EPI_\w+)\s*=\s*(\d+)", text))
+    assert len(enum) == 8 and sorted(map(int, enum.values())) == list(range(8))
+    for name, value in enum.items():
+        assert getattr(native, name) == int(value), name
+    # only the header carries the number
+    assert not re.search(r"return\s+\d+\s*;", re.search(r"int st_version\(void\)[^\n]*", _source("st_misc.hip")).group(0))
+    assert not re.search(r"^ABI_VERSION\s*=\s*\d", open(native.__file__).read(), flags=re.M)
+
+
+def test_a_missing_header_is_a_broken_checkout(monkeypatch, tmp_path):
+    monkeypatch.setattr(build, "ABI_HEADER", str(tmp_path / "nowhere" / "st_hip.h"))
+    with pytest.raises(RuntimeError, match="broken checkout"):
+        native._read_header()
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc is not installed")
+def test_a_definition_that_disagrees_with_the_header_does_not_compile(tmp_path):
+    """One host-only syntax pass of st_gemm_sym.hip against a copy of the header whose st_gemm takes `long long ldx`."""
+    text = open(HEADER).read()
+    changed = text.replace("int st_gemm(st_stream_t stream, int x_cmajor, int y_cmajor, const void* X, int ldx,",
+                           "int st_gemm(st_stream_t stream, int x_cmajor, int y_cmajor, const void* X, long long ldx,")
+    assert changed != text
+    (tmp_path / "st_hip.h").write_text(changed)
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    flags = ["-I" + str(tmp_path) if f.startswith("-I") else f for f in build.FLAGS]      # the copy instead of include/
+    r = subprocess.run([hipcc] + flags + ["--cuda-host-only", "-fsyntax-only", os.path.join(build.CSRC, "st_gemm_sym.hip")],
+                       cwd=build.CSRC, capture_output=True, text=True)
+    assert r.returncode != 0 and "conflicting types for 'st_gemm'" in r.stderr, r.stderr[-2000:]
 
 
 def test_no_cpu_fallback():
     """The product path refuses CPU tensors instead of silently emulating."""
-    import pytest
     import torch
     import transformer.SubLayers as S
     ff = S.PositionwiseFeedForward(128, 256, dropout=0.0).eval()
@@ -47,7 +155,6 @@ def test_no_cpu_fallback():
 def test_generated_instruction_streams_are_the_generators_output(tmp_path):
     """csrc/st_attn_bwd64_*.inc are GENERATED (tools/gen_attn_bwd64.py): the committed files must be what the committed
     generator writes, byte for byte (no hand edit of either side goes unnoticed)."""
-    import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if not k.startswith("BWD64_")}      # the development knobs change the output
     subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_attn_bwd64.py"), str(tmp_path)], check=True, env=env,

@@ -300,6 +300,121 @@ def test_attention_backward_key_split_across_workgroups_is_reproducible():
     assert int(work[:4096].abs().sum()) == 0, "tickets not reset"
 
 
+def _xattn_bwd_problem(q_lens, k_lens, seed):
+    """A decoder-encoder attention backward in its one-launch form (O = None, parts = 3; 4 heads of 64) on the GPU: the call's
+    arguments, its outputs, and the fp32 torch gradients of the same bf16 inputs."""
+    c = _attn_case(len(q_lens), 4, 64, q_lens, k_lens, False, True, seed=seed)
+    H, Mq, dk = c["H"], c["Mq"], 64
+    meta = [cu(c[k]) for k in ("q_off", "q_len", "k_off", "k_len")]
+    Q, K, V, dO = cu(c["Q"]), cu(c["K"]), cu(c["V"]), cu(c["dO"])
+    O, lse = torch.zeros(Mq, c["d"], dtype=BF16, device="cuda"), torch.zeros(H * Mq, dtype=F32, device="cuda")
+    nv.attn_fwd(Q, K, V, O, lse, *meta, H, c["max_q"], False, c["scale"], max_k=c["max_k"])
+    delta = (dO.float() * O.float()).view(Mq, H, dk).sum(-1).t().contiguous().view(-1)
+    out = [torch.zeros(Mq, c["d"], dtype=BF16, device="cuda")] + [torch.zeros(c["Mk"], c["d"], dtype=BF16, device="cuda") for _ in range(2)]
+    ref = [torch.zeros_like(t, dtype=F32) for t in out]
+    for b in range(len(q_lens)):
+        qs = slice(int(c["q_off"][b]), int(c["q_off"][b]) + q_lens[b])
+        ks = slice(int(c["k_off"][b]), int(c["k_off"][b]) + k_lens[b])
+        for h in range(H):
+            cs = slice(h * dk, (h + 1) * dk)
+            q, k, v, do = Q[qs, cs].float(), K[ks, cs].float(), V[ks, cs].float(), dO[qs, cs].float()
+            p = torch.softmax(q @ k.t() * c["scale"], -1)
+            dp = do @ v.t()
+            ds = p * (dp - (dp * p).sum(-1, keepdim=True))
+            ref[0][qs, cs], ref[1][ks, cs], ref[2][ks, cs] = ds @ k * c["scale"], ds.t() @ q * c["scale"], p.t() @ do
+    run = lambda: nv.attn_bwd(Q, K, V, None, dO, lse, delta, *out, *meta, H, c["max_q"], c["max_k"], False, c["scale"], parts=3)
+    return c, run, out, ref
+
+
+def test_attention_backward_scratch_outlives_the_graphs_that_captured_it():
+    """The key-split scratch is process-wide and its address is baked into every captured st_attn_bwd node: when a larger problem
+    makes it grow, the superseded buffer must stay allocated (native._scratch appends, never replaces) - a graph captured before
+    the growth still writes its tickets and fp32 partials there.  Capture a small problem (784 KiB of scratch), grow the scratch
+    with a large one (8,208 KiB), hand the allocator every chance to reuse a freed block, replay the old graph."""
+    key = torch.cuda.current_device()
+    earlier = nv._ATTN_SPLIT_WORK.pop(key, None)           # (what other tests left: this one must see the first use and the growth)
+    try:
+        kib = nv.load()._cdll.st_attn_bwd_split_kib
+        assert kib(4, 4, 64, 50, 300, 0) == 784 and kib(32, 4, 64, 50, 1000, 0) == 8208
+        c, run, out, ref = _xattn_bwd_problem([50, 33, 41, 7], [300, 257, 280, 129], seed=5)
+        assert (c["max_q"], c["max_k"]) == (50, 300)
+        run()                                       # eager: the scratch is born outside any capture
+        torch.cuda.synchronize()
+        old = nv._ATTN_SPLIT_WORK[key]
+        assert old.numel() * 4 == 784 * 1024
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            run()
+        assert nv._ATTN_SPLIT_WORK[key] is old
+        graph.replay()
+        torch.cuda.synchronize()
+        first = [t.clone() for t in out]
+        gen = torch.Generator().manual_seed(9)
+        big_q = [50] + torch.randint(1, 51, (31,), generator=gen).tolist()
+        big_k = [1000] + torch.randint(256, 1001, (31,), generator=gen).tolist()
+        cb, run_big, out_big, ref_big = _xattn_bwd_problem(big_q, big_k, seed=6)
+        assert (cb["max_q"], cb["max_k"]) == (50, 1000)
+        run_big()                                   # the scratch grows
+        torch.cuda.synchronize()
+        new = nv._ATTN_SPLIT_WORK[key]
+        assert new is not old and new.numel() * 4 >= 8208 * 1024 and new.data_ptr() != old.data_ptr()
+        assert any(t is old for t in nv._SUPERSEDED), "the superseded scratch is no longer referenced"
+        junk = [torch.full((old.numel(),), 0x5A5A5A5A, dtype=torch.int32, device="cuda") for _ in range(4)]     # would reuse a freed block
+        assert all(j.data_ptr() != old.data_ptr() for j in junk)
+        for t in out:
+            t.fill_(float("nan"))
+        graph.replay()
+        torch.cuda.synchronize()
+        for got, was, want, nm in zip(out, first, ref, ("dQ", "dK", "dV")):
+            print("replay after growth: %s rel-L2 vs fp32 torch %.3e" % (nm, rel(got, want)))
+            assert torch.equal(got, was), "%s of the replay changed after the scratch grew" % nm
+            check(got, want, 8e-3, "captured key-split backward after the scratch grew vs fp32 torch: %s" % nm)
+        for got, want, nm in zip(out_big, ref_big, ("dQ", "dK", "dV")):
+            check(got, want, 8e-3, "key-split backward on the grown scratch vs fp32 torch: %s" % nm)
+        assert int(old[:4096].abs().sum()) == 0 and int(new[:4096].abs().sum()) == 0, "tickets not reset"
+        assert all(int((j != 0x5A5A5A5A).sum()) == 0 for j in junk)
+    finally:
+        if earlier is not None:                   # (other tests' graphs may hold its address: it stays referenced either way)
+            mine = nv._ATTN_SPLIT_WORK.get(key)
+            keep, drop = (earlier, mine) if mine is None or mine.numel() < earlier.numel() else (mine, earlier)
+            nv._ATTN_SPLIT_WORK[key] = keep
+            if drop is not None:
+                nv._SUPERSEDED.append(drop)
+
+
+def test_attention_backward_scratch_first_used_inside_a_capture_is_not_kept():
+    """No warm-up before the capture (tests/test_fullsize_gpu.py captures with graph_warmup=0): the call allocates its scratch from
+    the capturing graph's pool, zero-fill included in the graph, and native._scratch does NOT adopt it as the process-wide one."""
+    key = torch.cuda.current_device()
+    earlier = nv._ATTN_SPLIT_WORK.pop(key, None)
+    try:
+        c, run, out, ref = _xattn_bwd_problem([50, 33, 41, 7], [300, 257, 280, 129], seed=5)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            run()
+        assert nv._ATTN_SPLIT_WORK.get(key) is None, "a buffer from a graph's private pool became the process-wide scratch"
+        for _ in range(2):
+            for t in out:
+                t.fill_(float("nan"))
+            graph.replay()
+        torch.cuda.synchronize()
+        captured = [t.clone() for t in out]
+        run()                                       # eager, on a scratch of the process's own
+        torch.cuda.synchronize()
+        assert nv._ATTN_SPLIT_WORK[key].numel() * 4 == 784 * 1024
+        for got, was, want, nm in zip(out, captured, ref, ("dQ", "dK", "dV")):
+            assert torch.equal(got, was), nm
+            check(got, want, 8e-3, "key-split backward captured without a warm-up vs fp32 torch: %s" % nm)
+    finally:
+        if earlier is not None:                   # (other tests' graphs may hold its address: it stays referenced either way)
+            mine = nv._ATTN_SPLIT_WORK.get(key)
+            keep, drop = (earlier, mine) if mine is None or mine.numel() < earlier.numel() else (mine, earlier)
+            nv._ATTN_SPLIT_WORK[key] = keep
+            if drop is not None:
+                nv._SUPERSEDED.append(drop)
+
+
 @pytest.mark.parametrize("case", DELTA_CASES)
 @pytest.mark.parametrize("use_work", [False, True])
 def test_attention_bwd_delta_supplied(case, use_work):

@@ -1,5 +1,6 @@
-import sys, heapq
-sys.path.insert(0, "/root/repo/speech-tranformer-pytorch_amd")
+import os, sys, heapq
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(ROOT, "speech-tranformer-pytorch_amd"))
 from st_amd import synthetic
 _, _, in_len, _, _ = synthetic.make_batch(32, 1000, 50, 80, 4337, seed=0, t_min=500, l_min=25)
 L = in_len.tolist()

@@ -1,5 +1,5 @@
 import os, sys, math, torch
-ROOT='/root/repo'
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (ROOT, os.path.join(ROOT, "speech-tranformer-pytorch_amd")): sys.path.insert(0, p)
 from st_amd import native as nv, synthetic, chains
 from st_amd.functional import Rows, attn_work

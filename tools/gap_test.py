@@ -1,5 +1,6 @@
-import sys, torch
-sys.path.insert(0, "/root/repo/speech-tranformer-pytorch_amd")
+import os, sys, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "speech-tranformer-pytorch_amd"))
 from st_amd import native as nv
 x = torch.zeros(64, dtype=torch.float32, device="cuda"); y = torch.zeros(64, dtype=torch.bfloat16, device="cuda")
 N = 400
