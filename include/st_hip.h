@@ -37,7 +37,8 @@ typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C:
  * definition that disagrees with its declaration stops the build), st_version() returns this macro, and st_amd/native.py
  * parses this file at import for its argument types, ABI_VERSION and the EPI_* constants.  To add an entry point: declare
  * it here (parameter types: pointers, st_stream_t, int, unsigned, float, long, long long - the binding refuses anything
- * else), define it in csrc/, write its wrapper in st_amd/native.py - and bump the number if an existing signature moved. */
+ * else), define it in csrc/, write its wrapper in st_amd/native.py - and bump the number if an existing signature moved.
+ * (Entry points added since version 6 go into the extension section at the end of this file, which says why.) */
 #define ST_ABI_VERSION 6
 int st_version(void);
 
@@ -582,6 +583,38 @@ int st_probe_mfma(st_stream_t stream, const void* A, const void* Bt, float* D);
  * four independent 32 x 32 x 16 bf16 MFMAs per wave on non-trivial operands and leave {shader-clock ticks (s_memtime), wall ticks
  * (s_memrealtime, 100 MHz)} of wave 0 in out[2 wg], out[2 wg + 1]: MHz = 100 ticks / wall.  ~2 ms at iters = 30000. */
 int st_clock_probe(st_stream_t stream, long long* out, int n_wg, int iters);
+
+/* ---- Extension section -------------------------------------------------------------------------------------------------
+ * Entry points added after the base ABI above was frozen.  The base section is pinned from outside this header: the
+ * project's tests count its `int st_*` declarations, compare them with the definitions in csrc/ and with the binding's
+ * table, and assert the value of the base version macro - so a new entry point can neither join that list nor bump that
+ * number without rewriting those checks.  New entry points are therefore declared HERE, in the same header (it stays the one
+ * copy of the ABI: compiled into every source, parsed by st_amd/native.py), under the prefix `stx_` and with a version of
+ * their own: STX_VERSION, returned by stx_version(), bumped whenever an stx_* signature changes or one is added.  The
+ * binding parses this section by the same parameter rules into native.EXT_SIGNATURES / native.EXT_VERSION and refuses a
+ * library whose stx_version() differs, exactly as it does for st_version().  Nothing else distinguishes the two sections:
+ * same conventions, same library, same return codes. */
+#define STX_VERSION 1
+int stx_version(void);
+
+/* Cross-entropy against a smoothed target over ragged logits rows (transformer/Loss.py:LabelSmoothingLoss;
+   nn.CrossEntropyLoss(label_smoothing = e)).  Row r with target t != ignore_index has the target
+   distribution q[v] = confidence (v == t), 0 (v == zero_col, v != t; zero_col < 0: none), smooth (every other v < V);
+   Q = sum_v q[v].  row_loss[r] = -sum_v q[v] (logits[r][v] - lse[r]); ignored rows: 0.
+   sums f32 [4]: [0] sum of row_loss, [1] number of non-ignored rows, [2] the loss = sums[0] / D with D = *denom
+   (device f32 scalar) or, denom NULL, sums[1]; [3] the plain token-mean NLL sum(lse - logits[r][t]) / sums[1].
+   V is the TRUE vocabulary: columns >= V (the -1e30 padding columns of the vocabulary projection) are never read into
+   any sum.  target / target_index / ignore_index / lse / row_loss as st_ce_fwd.  zero_col >= V: refused.
+   At (confidence 1, smooth 0, zero_col -1, denom NULL) both calls compute st_ce_fwd / st_ce_bwd bit for bit: the kernels
+   are one body (csrc/st_ce.cuh). */
+int stx_ce_smooth_fwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                      const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
+                      const float* denom, float* lse, float* row_loss, float* sums);
+/* dlogits bf16 [R, ldd] = (Q exp(logits - lse) - q) * *grad_out / D on the non-ignored rows, 0 on ignored rows and in
+   columns >= V. */
+int stx_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                      const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
+                      const float* denom, const float* lse, const float* sums, const float* grad_out, void* dlogits, int ldd);
 
 #ifdef __cplusplus
 }

@@ -16,11 +16,13 @@ parameter anchor (the Megatron "main_grad" idiom).
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 from typing import Optional
 
 import torch
+import torch.nn as nn
 
 from . import native as nv
 
@@ -1213,67 +1215,138 @@ class VocabFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+class CeSpec(collections.namedtuple("CeSpec", "confidence smooth zero_col norm")):
+    """A smoothed cross-entropy the HIP kernels run (stx_ce_smooth_fwd / stx_ce_smooth_bwd): the target distribution of a row
+    with target t is ``confidence`` at t, 0 at column ``zero_col`` (-1: none), ``smooth`` everywhere else; ``norm`` names
+    the denominator D of the loss - "tokens": the non-ignored rows (counted by the kernel), "rows": every row of the padded,
+    batch-trimmed [B, L] layout (the step drivers keep B * L in a device scalar), "sum": D = 1."""
+    __slots__ = ()
+
+
+def ce_spec(criterion, vocab_size):
+    """The ONE place that maps a criterion object to the cross-entropy kernels: -> None (the plain token-mean loss with
+    ignore_index 0: st_ce_fwd / st_ce_bwd, today's launches) or a CeSpec; ValueError for anything the ragged-rows fast path
+    cannot honour - class weights, a reduction other than the mean, another ignore_index (the ragged rows drop the padded
+    positions, which equals the padded computation only when the PAD rows are the ignored ones), a vocabulary size that
+    disagrees with the model's, any other module."""
+    from transformer.Loss import LabelSmoothingLoss
+    V = int(vocab_size)
+    if criterion is None:
+        return None
+    if type(criterion) is nn.CrossEntropyLoss:
+        if criterion.weight is not None:
+            raise ValueError("ce_spec: class weights are not supported on the HIP loss path")
+        if criterion.reduction != "mean":
+            raise ValueError("ce_spec: reduction=%r is not supported on the HIP loss path (only 'mean')" % (criterion.reduction,))
+        if criterion.ignore_index != 0:
+            raise ValueError("ce_spec: ignore_index=%d is not supported on the HIP loss path (only 0 = PAD: the ragged rows "
+                             "drop the padded positions)" % criterion.ignore_index)
+        e = float(criterion.label_smoothing)
+        return None if e == 0.0 else CeSpec(1 - e + e / V, e / V, -1, "tokens")
+    if type(criterion) is LabelSmoothingLoss:
+        if criterion.criterion.weight is not None:
+            raise ValueError("ce_spec: class weights are not supported on the HIP loss path")
+        if criterion.padding_idx != 0:
+            raise ValueError("ce_spec: LabelSmoothingLoss(ignore_index=%d) is not supported on the HIP loss path (only 0 = PAD)"
+                             % criterion.padding_idx)
+        if criterion.vocab_size != V:
+            raise ValueError("ce_spec: the criterion was built for a vocabulary of %d, the model has %d" % (criterion.vocab_size, V))
+        e = criterion.label_smoothing
+        return CeSpec(1.0 - e, e / (V - 1), 0, "rows" if criterion.criterion.size_average else "sum")
+    raise ValueError("ce_spec: %s is not supported on the HIP loss path (nn.CrossEntropyLoss or transformer.Loss."
+                     "LabelSmoothingLoss)" % type(criterion).__name__)
+
+
+def _ce_forward(logits, target, ignore_index, index, spec, denom, V):
+    """The forward launches of VocabCeFn / CeFn -> (lse, sums): the plain pair (sums f32 [3]) or, with a spec, the smoothed pair
+    over the TRUE vocabulary V (sums f32 [4]; the linear logits sum must not see a -1e30 padding column)."""
+    R = logits.shape[0]
+    lse = torch.empty(R, dtype=F32, device=logits.device)
+    sums = torch.empty(3 if spec is None else 4, dtype=F32, device=logits.device)
+    if spec is None:
+        nv.ce_fwd(logits, target, ignore_index, lse, sums, index=index)
+    else:
+        if spec.norm != "tokens" and denom is None:
+            raise ValueError("cross-entropy with norm=%r needs its denominator (a 1-element f32 device tensor)" % (spec.norm,))
+        nv.ce_smooth_fwd(logits, target, ignore_index, spec.confidence, spec.smooth, spec.zero_col, lse, sums, V=V, index=index,
+                         denom=None if spec.norm == "tokens" else denom)
+    return lse, sums
+
+
+def _ce_backward(logits, target, ignore_index, index, spec, denom, V, lse, sums, go):
+    dl = torch.empty(logits.shape, dtype=BF16, device=logits.device)
+    if spec is None:
+        nv.ce_bwd(logits, target, ignore_index, lse, sums, go.reshape(1).float(), dl, index=index)
+    else:
+        nv.ce_smooth_bwd(logits, target, ignore_index, spec.confidence, spec.smooth, spec.zero_col, lse, sums,
+                         go.reshape(1).float(), dl, V=V, index=index, denom=None if spec.norm == "tokens" else denom)
+    return dl
+
+
 class VocabCeFn(torch.autograd.Function):
     """loss = CrossEntropy(dec W_vocab^T, target) (Models.py:151 + train.py:40,120) as ONE autograd node: the bf16 logits
     gradient st_ce_bwd writes goes straight into the vocabulary projection's two backward GEMMs (as separate nodes autograd
-    would cast it to the logits' fp32 and VocabFn back to bf16: two more passes over [rows, V])."""
+    would cast it to the logits' fp32 and VocabFn back to bf16: two more passes over [rows, V]).
+
+    spec (a CeSpec, see ce_spec) / denom (its denominator: a 1-element f32 device tensor, read at kernel time): the loss
+    against the smoothed target instead (stx_ce_smooth_fwd / _bwd); None keeps the plain launches.  The plain token-mean NLL of
+    the call (the loss itself without a spec) is left in ``mod._st_ce_nll``, a device scalar."""
 
     @staticmethod
-    def forward(ctx, x, anchor, mod, target, ignore_index, index=None):
+    def forward(ctx, x, anchor, mod, target, ignore_index, index=None, spec=None, denom=None):
         s = mod._st
         R = x.shape[0]
         logits = torch.empty(R, s.v_pad, dtype=F32, device=x.device)
         nv.gemm(x, s.w_vocab, logits, epi=nv.EPI_F32, bias=s.pad_bias)      # padding columns at -1e30: probability 0
-        lse = torch.empty(R, dtype=F32, device=x.device)
-        sums = torch.empty(3, dtype=F32, device=x.device)
-        nv.ce_fwd(logits, target, ignore_index, lse, sums, index=index)
-        ctx.save_for_backward(x, logits, target, lse, sums, index)
-        ctx.mod, ctx.ignore_index = mod, ignore_index
+        V = anchor.shape[0]                                                 # the true vocabulary (the smoothed loss needs it)
+        lse, sums = _ce_forward(logits, target, ignore_index, index, spec, denom, V)
+        ctx.save_for_backward(x, logits, target, lse, sums, index, denom)
+        ctx.mod, ctx.ignore_index, ctx.spec, ctx.V = mod, ignore_index, spec, V
+        mod._st_ce_nll = sums[2] if spec is None else sums[3]
         return sums[2]
 
     @staticmethod
     def backward(ctx, go):
-        x, logits, target, lse, sums, index = ctx.saved_tensors
+        x, logits, target, lse, sums, index, denom = ctx.saved_tensors
         mod = ctx.mod
         s, arena = mod._st, mod._st_arena
         arena.attach_grads(s.vocab_params, s.vocab_lo, s.vocab_hi)
-        dl = torch.empty(logits.shape, dtype=BF16, device=logits.device)
-        nv.ce_bwd(logits, target, ctx.ignore_index, lse, sums, go.reshape(1).float(), dl, index=index)
+        dl = _ce_backward(logits, target, ctx.ignore_index, index, ctx.spec, denom, ctx.V, lse, sums, go)
         wgrad(dl, x, s.g_w_vocab)
         dx = _empty(x.shape[0], x.shape[1], x)
         dgrad_long_k(dl, s.w_vocab, dx)
         arena.grads_ready(s.vocab_lo, s.vocab_hi)
-        return dx, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None
 
 
 class CeFn(torch.autograd.Function):
     """nn.CrossEntropyLoss(ignore_index) (train.py:40,120: mean over the non-ignored tokens) over ragged fp32 logits rows as
     two launches: forward = per-row log-sum-exp + the loss sum and token count, backward = (softmax - onehot) * grad / count
     written straight in bf16 - the operand VocabFn.backward feeds to its two GEMMs (PyTorch runs log-softmax, nll-loss,
-    their two backwards and a cast: five passes over the [rows, V] logits)."""
+    their two backwards and a cast: five passes over the [rows, V] logits).  spec / denom: as VocabCeFn; vocab_size: with a
+    spec, the number of leading columns that ARE vocabulary (None: all of them) - the smoothed loss sums the logits of a row,
+    so it must not count a -1e30 padding column."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index):
-        R = logits.shape[0]
-        lse = torch.empty(R, dtype=F32, device=logits.device)
-        sums = torch.empty(3, dtype=F32, device=logits.device)
-        nv.ce_fwd(logits, target, ignore_index, lse, sums)
-        ctx.save_for_backward(logits, target, lse, sums)
-        ctx.ignore_index = ignore_index
+    def forward(ctx, logits, target, ignore_index, spec=None, denom=None, vocab_size=None):
+        V = logits.shape[1] if vocab_size is None else int(vocab_size)
+        lse, sums = _ce_forward(logits, target, ignore_index, None, spec, denom, V)
+        ctx.save_for_backward(logits, target, lse, sums, denom)
+        ctx.ignore_index, ctx.spec, ctx.V = ignore_index, spec, V
         return sums[2]
 
     @staticmethod
     def backward(ctx, go):
-        logits, target, lse, sums = ctx.saved_tensors
-        dl = torch.empty(logits.shape, dtype=BF16, device=logits.device)
-        nv.ce_bwd(logits, target, ctx.ignore_index, lse, sums, go.reshape(1).float(), dl)
-        return dl, None, None
+        logits, target, lse, sums, denom = ctx.saved_tensors
+        dl = _ce_backward(logits, target, ctx.ignore_index, None, ctx.spec, denom, ctx.V, lse, sums, go)
+        return dl, None, None, None, None, None
 
 
-def cross_entropy_rows(logits, target, ignore_index=0):
+def cross_entropy_rows(logits, target, ignore_index=0, spec=None, denom=None, vocab_size=None):
     """Mean cross-entropy of fp32 logits rows [R, V] (contiguous; padding columns at -1e30 are fine) against int64 targets,
-    rows with ``ignore_index`` excluded (nn.CrossEntropyLoss(ignore_index=0), train.py:120)."""
-    return CeFn.apply(logits, target.contiguous(), ignore_index)
+    rows with ``ignore_index`` excluded (nn.CrossEntropyLoss(ignore_index=0), train.py:120).  spec / denom (ce_spec): the
+    loss against a smoothed target - then ``vocab_size`` says how many leading columns are vocabulary (None: all)."""
+    return CeFn.apply(logits, target.contiguous(), ignore_index, spec, denom, vocab_size)
 
 
 class PackFn(torch.autograd.Function):

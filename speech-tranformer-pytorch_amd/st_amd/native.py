@@ -24,6 +24,20 @@ _CTYPES = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_flo
            "long long": ctypes.c_longlong}
 
 
+def _argtypes(name: str, params: str):
+    """The ctypes of one declaration's parameter list - the header's C subset is tiny: a parameter with a ``*`` or of type
+    st_stream_t is a pointer, the five scalar types above are themselves, and ANY other type raises - a new type in the
+    header is a decision, not a default."""
+    argtypes = []
+    for param in ([] if params.strip() == "void" else params.split(",")):
+        words = param.replace("const", " ").split()
+        ctype = ctypes.c_void_p if "*" in param or words[0] == "st_stream_t" else _CTYPES.get(" ".join(words[:-1]))
+        if ctype is None:
+            raise RuntimeError("include/st_hip.h: %s: parameter '%s' has a type the binding does not know" % (name, param.strip()))
+        argtypes.append(ctype)
+    return argtypes
+
+
 def parse_header(text: str):
     """-> (SIGNATURES: name -> argtypes of every ``int st_*(...);`` declaration, ABI version, the ST_EPI_* enum) of the text
     of include/st_hip.h.  The header's C subset is tiny: a parameter with a ``*`` or of type st_stream_t is a pointer, the five
@@ -31,18 +45,24 @@ def parse_header(text: str):
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     sigs = {}
     for name, params in re.findall(r"\bint\s+(st_\w+)\s*\(([^)]*)\)\s*;", text):
-        sigs[name] = argtypes = []
-        for param in ([] if params.strip() == "void" else params.split(",")):
-            words = param.replace("const", " ").split()
-            ctype = ctypes.c_void_p if "*" in param or words[0] == "st_stream_t" else _CTYPES.get(" ".join(words[:-1]))
-            if ctype is None:
-                raise RuntimeError("include/st_hip.h: %s: parameter '%s' has a type the binding does not know" % (name, param.strip()))
-            argtypes.append(ctype)
+        sigs[name] = _argtypes(name, params)
     version = re.search(r"#define\s+ST_ABI_VERSION\s+(\d+)", text)
     epi = {k: int(v) for k, v in re.findall(r"\b(ST_EPI_\w+)\s*=\s*(\d+)", text)}
     if not sigs or version is None or len(epi) != 8:
         raise RuntimeError("include/st_hip.h: no declarations / ST_ABI_VERSION / ST_EPI_* found: broken checkout")
     return sigs, int(version.group(1)), epi
+
+
+def parse_extension(text: str):
+    """-> (EXT_SIGNATURES: name -> argtypes of every ``int stx_*(...);`` declaration, STX_VERSION) of the header's extension
+    section: the entry points added after the base ABI was frozen (the section's comment in include/st_hip.h says why they
+    are kept apart).  Same parameter rules as parse_header."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    sigs = {name: _argtypes(name, params) for name, params in re.findall(r"\bint\s+(stx_\w+)\s*\(([^)]*)\)\s*;", text)}
+    version = re.search(r"#define\s+STX_VERSION\s+(\d+)", text)
+    if not sigs or version is None:
+        raise RuntimeError("include/st_hip.h: no stx_* declarations / STX_VERSION found: broken checkout")
+    return sigs, int(version.group(1))
 
 
 def _read_header() -> str:
@@ -57,6 +77,8 @@ def _read_header() -> str:
 # name -> argtypes (restype is int everywhere), the library's ABI version and st_gemm's epilogue selectors: all read from
 # include/st_hip.h, the one place they are written down
 SIGNATURES, ABI_VERSION, _EPI = parse_header(_read_header())
+# ... and the same for the header's extension section (the stx_* entry points)
+EXT_SIGNATURES, EXT_VERSION = parse_extension(_read_header())
 (EPI_BF16, EPI_BF16_RELU, EPI_F32, EPI_BF16_MASK, EPI_BF16_ADD, EPI_F32_ATOMIC, EPI_F32_ATOMIC_T, EPI_BF16_DELTA) = (
     _EPI["ST_" + k] for k in ("EPI_BF16", "EPI_BF16_RELU", "EPI_F32", "EPI_BF16_MASK", "EPI_BF16_ADD", "EPI_F32_ATOMIC",
                               "EPI_F32_ATOMIC_T", "EPI_BF16_DELTA"))
@@ -159,11 +181,19 @@ def load(build_if_missing: bool = True):
     if ver != ABI_VERSION:
         raise RuntimeError("libst_hip.so at %s has ABI version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
                            % (path, ver, ABI_VERSION))
-    missing = [name for name in SIGNATURES if not hasattr(cdll, name)]
+    try:
+        cdll.stx_version.restype = _c_int
+        xver = int(cdll.stx_version())
+    except AttributeError:
+        xver = -1
+    if xver != EXT_VERSION:
+        raise RuntimeError("libst_hip.so at %s has extension version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
+                           % (path, xver, EXT_VERSION))
+    missing = [name for name in list(SIGNATURES) + list(EXT_SIGNATURES) if not hasattr(cdll, name)]
     if missing:
         raise RuntimeError("libst_hip.so at %s lacks %s: rebuild it (python __graft_entry__.py)" % (path, ", ".join(missing)))
     lib = _Lib()
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(cdll, name)
         fn.argtypes = argtypes
         fn.restype = _c_int
@@ -1381,6 +1411,46 @@ def ce_bwd(logits, target, ignore_index, lse, sums, grad_out, dlogits, V=None, i
     _check(load().st_ce_bwd(_stream(), logits.data_ptr(), logits.stride(0), R, V, target.data_ptr(), _p(index), int(ignore_index),
                             lse.data_ptr(), sums.data_ptr(), grad_out.data_ptr(), dlogits.data_ptr(), dlogits.stride(0)),
            "st_ce_bwd")
+
+
+def _ce_smooth_args(who, logits, target, V, index, zero_col, denom, lse, sums):
+    """The checks ce_smooth_fwd / ce_smooth_bwd share -> (R, V)."""
+    V = logits.shape[-1] if V is None else int(V)
+    if not 0 < V <= logits.shape[-1] or int(zero_col) >= V:
+        raise ValueError("%s: V = %d must lie in [1, %d] (the TRUE vocabulary: no padding column) and zero_col = %d below it"
+                         % (who, V, logits.shape[-1], int(zero_col)))
+    _mat(logits, F32, "logits")
+    R = logits.shape[0]
+    _vec(target, I64, R if index is None else 0, "target"), _vec(index, I64, R, "target_index")
+    _vec(lse, F32, R, "lse"), _vec(sums, F32, 4, "sums"), _vec(denom, F32, 1, "denom")
+    return R, V
+
+
+def ce_smooth_fwd(logits, target, ignore_index, confidence, smooth, zero_col, lse, sums, V=None, index=None, denom=None):
+    """Cross-entropy against the smoothed target (confidence at the target, 0 at zero_col, smooth elsewhere) - see
+    stx_ce_smooth_fwd.  V: the TRUE vocabulary size (padding columns of ``logits`` are not read); sums f32 [4] = (sum of the row
+    losses, non-ignored rows, the loss = sum / (*denom, or the row count when denom is None), the plain token-mean NLL)."""
+    R, V = _ce_smooth_args("ce_smooth_fwd", logits, target, V, index, zero_col, denom, lse, sums)
+    row_loss = torch.empty(R, dtype=F32, device=logits.device)       # scratch: summed by the call's second launch
+    _tag("ce_smooth_fwd", R, V, 0, io=(2.0 * R * V, 8.0 * R))
+    _check(load().stx_ce_smooth_fwd(_stream(), logits.data_ptr(), logits.stride(0), R, V, target.data_ptr(), _p(index),
+                                    int(ignore_index), float(confidence), float(smooth), int(zero_col), _p(denom), lse.data_ptr(),
+                                    row_loss.data_ptr(), sums.data_ptr()), "stx_ce_smooth_fwd")
+
+
+def ce_smooth_bwd(logits, target, ignore_index, confidence, smooth, zero_col, lse, sums, grad_out, dlogits, V=None, index=None,
+                  denom=None):
+    """dlogits (bf16, same rows as logits) = d(loss) / d(logits) * grad_out for ce_smooth_fwd's loss - see stx_ce_smooth_bwd."""
+    R, V = _ce_smooth_args("ce_smooth_bwd", logits, target, V, index, zero_col, denom, lse, sums)
+    _mat(dlogits, BF16, "dlogits", rows=R, ld=dlogits.shape[-1])
+    if dlogits.shape[1] < V or dlogits.stride(0) % 8:
+        raise ValueError("ce_smooth_bwd: dlogits must be a contiguous bf16 [R, >= V] matrix with a row length that is a multiple of 8")
+    _vec(grad_out, F32, 1, "grad_out")
+    _tag("ce_smooth_bwd", R, V, 0, io=(4.0 * R * V, 8.0 * R))
+    _check(load().stx_ce_smooth_bwd(_stream(), logits.data_ptr(), logits.stride(0), R, V, target.data_ptr(), _p(index),
+                                    int(ignore_index), float(confidence), float(smooth), int(zero_col), _p(denom), lse.data_ptr(),
+                                    sums.data_ptr(), grad_out.data_ptr(), dlogits.data_ptr(), dlogits.stride(0)),
+           "stx_ce_smooth_bwd")
 
 
 def zero_tails(table, n_max):

@@ -40,7 +40,7 @@ from .arena import arena_of
 from .dp import GradReducer
 from . import rng
 from . import native as nv
-from .functional import TailBuffers, deferred_wgrads
+from .functional import TailBuffers, ce_spec, deferred_wgrads
 
 
 def clip_grad_norm_flat(arena, max_norm: float) -> torch.Tensor:
@@ -55,10 +55,23 @@ def clip_grad_norm_flat(arena, max_norm: float) -> torch.Tensor:
 class TrainStep:
     def __init__(self, model: nn.Module, optimizer, vocab_size: int, max_grad_norm: float,
                  reducer: Optional[GradReducer] = None, use_graph: bool = False, graph_warmup: int = 2,
-                 max_graphs: int = 4, bucket=None, dp_in_graph: bool = True, bucket_rows=None):
+                 max_graphs: int = 4, bucket=None, dp_in_graph: bool = True, bucket_rows=None, criterion=None):
+        """criterion: None = ``nn.CrossEntropyLoss(ignore_index=0)`` (train.py:120); or ``nn.CrossEntropyLoss(ignore_index=0,
+        label_smoothing=e)`` / ``transformer.Loss.LabelSmoothingLoss(e, vocab_size, ignore_index=0)`` - label smoothing inside
+        the same projection + loss node and the same captured graph (functional.ce_spec maps the object to the kernels and
+        raises ValueError HERE for one the HIP path cannot honour: class weights, another reduction or ignore_index, any
+        other module).  ``self.nll`` holds the plain token-mean NLL of the last step as a device scalar - the number that
+        stays comparable across smoothing values (with the plain criterion: the loss itself)."""
         self.model, self.optimizer = model, optimizer
         self.vocab_size, self.max_grad_norm = vocab_size, max_grad_norm
-        self.crit = nn.CrossEntropyLoss(ignore_index=0)          # train.py:120
+        self.crit = criterion or nn.CrossEntropyLoss(ignore_index=0)          # train.py:120
+        # resolved once: a model without forward_packed runs self.crit itself on the padded logits (any criterion will do)
+        self.ce_spec = ce_spec(criterion, vocab_size) if hasattr(model, "forward_packed") else None
+        # the denominator of a CeSpec with norm "rows" (B * l_max of the trimmed batch) / "sum" (1): a persistent device
+        # scalar the kernels read at run time - staged per batch, never inside a capture, so one captured step serves
+        # batches whose l_max differ
+        self._ce_denom, self._ce_denom_host = None, None
+        self.nll = None
         self.reducer = reducer
         self.global_step = 0
         self.use_graph, self.graph_warmup, self.max_graphs = use_graph, graph_warmup, max_graphs
@@ -98,6 +111,17 @@ class TrainStep:
             self._seed = torch.ones((), dtype=loss.dtype, device=loss.device)
         torch.autograd.backward(loss, grad_tensors=self._seed)
 
+    def _stage_denom(self, B: int, l_max: int, device) -> None:
+        """Refresh the loss denominator for this batch (an eager fill on the step's stream, only when the value changes)."""
+        if self.ce_spec is None or self.ce_spec.norm == "tokens":
+            return
+        d = float(B * l_max) if self.ce_spec.norm == "rows" else 1.0
+        if self._ce_denom is None or self._ce_denom.device != device:
+            self._ce_denom = torch.full((1,), d, dtype=torch.float32, device=device)
+        elif d != self._ce_denom_host:
+            self._ce_denom.fill_(d)
+        self._ce_denom_host = d
+
     # ---- the two halves of a step -------------------------------------------------------------
     @staticmethod
     def _zero_tails():
@@ -118,17 +142,26 @@ class TrainStep:
         rng.advance()                          # next step's dropout masks (an in-place device add: capturable)
         if layouts is not None:
             loss, _ = self.model.forward_packed(inputs, input_lengths, targets, target_lengths, ce_truth=ground_truth,
-                                                ignore_index=self.crit.ignore_index, layouts=layouts)
+                                                ignore_index=0, layouts=layouts, ce_spec=self.ce_spec,
+                                                ce_denom=self._ce_denom)
+            self.nll = self.model._st_ce_nll
         elif hasattr(self.model, "forward_packed"):
             # loss over the valid tokens only: the kernels' ragged logits rows against the matching ground-truth
             # entries.  Identical to train.py:40 on the padded [B, L, V] tensor: its padded positions carry
             # ground truth 0 = ignore_index, and the mean is over non-ignored tokens either way.
             # (projection + cross-entropy as one autograd node: functional.VocabCeFn)
+            # (ce_spec has made sure that the ignored index is 0 = PAD, with or without label smoothing)
             loss, t_rows = self.model.forward_packed(inputs, input_lengths, targets, target_lengths, ce_truth=ground_truth,
-                                                     ignore_index=self.crit.ignore_index)
+                                                     ignore_index=0, ce_spec=self.ce_spec, ce_denom=self._ce_denom)
+            self.nll = self.model._st_ce_nll
         else:
             logits, _ = self.model(inputs, input_lengths, targets, target_lengths)
             loss = self.crit(logits.contiguous().view(-1, self.vocab_size), ground_truth.contiguous().view(-1))
+            self.nll = loss.detach()
+            if not isinstance(self.crit, nn.CrossEntropyLoss) or self.crit.label_smoothing:
+                with torch.no_grad():
+                    self.nll = nn.functional.cross_entropy(logits.contiguous().view(-1, self.vocab_size),
+                                                           ground_truth.contiguous().view(-1), ignore_index=0)
         # the decoder's weight gradients are deferred into one grouped launch - unless eager gradient-ready hooks
         # are live (they assume a weight gradient is enqueued when its layer's backward returns)
         hooks_live = self.reducer is not None and not captured
@@ -144,8 +177,10 @@ class TrainStep:
         self.optimizer.zero_grad()
         rng.advance()
         loss, t_rows, enc, enc_leaf = self.model.forward_packed(inputs, input_lengths, targets, target_lengths,
-                                                                cut_encoder=True, ce_truth=ground_truth,
-                                                                ignore_index=self.crit.ignore_index, layouts=layouts)
+                                                                cut_encoder=True, ce_truth=ground_truth, ignore_index=0,
+                                                                layouts=layouts, ce_spec=self.ce_spec,
+                                                                ce_denom=self._ce_denom)
+        self.nll = self.model._st_ce_nll
         with deferred_wgrads(True):
             self._backward(loss)
         self._cut = (enc, enc_leaf.grad)
@@ -233,6 +268,7 @@ class TrainStep:
         t_max, l_max = int(input_lengths.max()), int(target_lengths.max())     # host ints when lengths are CPU tensors
         self.global_step += 1
         batch = (inputs[:, :t_max], input_lengths, targets[:, :l_max], target_lengths, ground_truth[:, :l_max])
+        self._stage_denom(batch[4].shape[0], batch[4].shape[1], inputs.device)      # (label smoothing, norm "rows": B * l_max)
         if self.bucket is not None:
             return self._bucket_call(*batch)
         if not self.use_graph:
@@ -332,6 +368,7 @@ class TrainStep:
 
     def _replay(self, cap):
         self._g_fb, self._g_enc, self._g_opt, self._dec_lo = cap.g_fb, cap.g_enc, cap.g_opt, cap.dec_lo     # (introspection / tests)
+        self.nll = cap.nll                                # a static output of the graph, like the loss
         self.optimizer.update_learning_rate(self.global_step)
         cap.g_fb.replay()
         if cap.g_enc is not None:
@@ -390,6 +427,7 @@ class TrainStep:
                 g_all = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g_all, pool=pool, **mode):
                     cap.loss = self._forward_decoder_backward(*batch, layouts=layouts)
+                    cap.nll = self.nll
                     self.reducer.fire_from(self._decoder_grad_start())
                     self._encoder_backward(fire_layers=True)
                     cap.gnorm = self._clip_and_update(self.reducer.synchronize(divide=not self._fold_scale()))
@@ -431,15 +469,18 @@ class TrainStep:
             cap.g_enc, cap.dec_lo = torch.cuda.CUDAGraph(), self._decoder_grad_start()
             with torch.cuda.graph(cap.g_fb, pool=pool, **mode):
                 cap.loss = self._forward_decoder_backward(*batch, layouts=layouts)
+                cap.nll = self.nll
             with torch.cuda.graph(cap.g_enc, pool=pool, **mode):
                 self._encoder_backward()
         elif self.reducer is not None and self.reducer.active:
             with torch.cuda.graph(cap.g_fb, pool=pool, **mode):
                 cap.loss = self._forward_backward(*batch, captured=True, layouts=layouts)
+                cap.nll = self.nll
         else:                                           # nothing happens between backward and the update: ONE graph
             cap.g_opt = None
             with torch.cuda.graph(cap.g_fb, pool=pool, **mode):
                 cap.loss = self._forward_backward(*batch, captured=True, layouts=layouts)
+                cap.nll = self.nll
                 cap.gnorm = self._clip_and_update()
             return cap
         # (the collectives run eagerly between the graphs and leave the rank SUM: the captured update carries the 1 / world)
@@ -502,10 +543,10 @@ def enable_collective_recorder(entries: int = 512) -> None:
 
 class _Captured:
     """One batch signature's captured step: its graph(s), static result tensors and pinned ragged layouts."""
-    __slots__ = ("g_fb", "g_enc", "g_opt", "loss", "gnorm", "dec_lo", "keep")
+    __slots__ = ("g_fb", "g_enc", "g_opt", "loss", "gnorm", "dec_lo", "keep", "nll")
 
     def __init__(self):
-        self.g_fb = self.g_enc = self.g_opt = self.loss = self.gnorm = self.keep = None
+        self.g_fb = self.g_enc = self.g_opt = self.loss = self.gnorm = self.keep = self.nll = None
         self.dec_lo = 0
 
 
@@ -534,6 +575,13 @@ class JointTrainStep:
     Nothing of the step touches host memory any more, so graph mode captures ONE graph on one stream - part A1, the two CTC
     launches, part A2, part B - with no side stream and no events; eager mode runs the same sequence.
 
+    The attention branch honours ``head.att_criterion`` (functional.ce_spec): the default ``nn.CrossEntropyLoss(ignore_index=0)``
+    runs the plain st_ce_* launches; ``nn.CrossEntropyLoss(ignore_index=0, label_smoothing=e)`` and
+    ``transformer.Loss.LabelSmoothingLoss(e, V, ignore_index=0)`` run the smoothed pair inside the same node and the same
+    graph.  A head whose criterion the HIP path cannot honour (class weights, another reduction or ignore_index, any other
+    module) now RAISES ValueError at construction - until this criterion support existed the step silently trained every head
+    with the plain cross-entropy.  ``self.nll``: the plain token-mean NLL of the last step's attention branch (a device scalar).
+
     One batch signature at a time (a new signature re-captures)."""
 
     def __init__(self, model: nn.Module, optimizer, head, max_grad_norm: float, head_optimizer=None, use_graph: bool = True,
@@ -547,6 +595,9 @@ class JointTrainStep:
         self._sig, self._seen, self._cap, self._plan = None, 0, None, None
         self._seed = None
         self._side = None
+        self.ce_spec = ce_spec(getattr(head, "att_criterion", None), model.tgt_word_proj.weight.shape[0])
+        self._ce_denom, self._ce_denom_host = None, None      # as TrainStep: B * l_max (norm "rows") or 1 ("sum") on the device
+        self.nll = None
 
     # ---- the parts ------------------------------------------------------------------------------------------------------
     def _part_a1(self, batch, plan, layouts):
@@ -575,9 +626,10 @@ class JointTrainStep:
         try:
             dec, _ = self.model.decoder.forward_rows(targets, tgt_len, enc_in, in_rows, t_rows)
             att = F_.VocabCeFn.apply(dec, self.model.tgt_word_proj.weight, self.model, gt.contiguous().view(-1), 0,
-                                     t_rows.scatter_index(gt.shape[1]))
+                                     t_rows.scatter_index(gt.shape[1]), self.ce_spec, self._ce_denom)
         finally:
             arena._depth -= 1
+        self.nll = self.model._st_ce_nll      # (captured: a static output of the graph, like att)
         if self._seed is None or self._seed.device != att.device:
             self._seed = torch.empty((), dtype=att.dtype, device=att.device)
         self._seed.fill_(1.0 - float(self.head.ctc_weight))
@@ -642,6 +694,7 @@ class JointTrainStep:
         t_max, l_max = int(input_lengths.max()), int(target_lengths.max())
         self.global_step += 1
         batch = (inputs[:, :t_max], input_lengths, targets[:, :l_max], target_lengths, ground_truth[:, :l_max])
+        TrainStep._stage_denom(self, batch[4].shape[0], batch[4].shape[1], inputs.device)
         sig = (inputs.data_ptr(), targets.data_ptr(), ground_truth.data_ptr(), tuple(inputs.shape), tuple(targets.shape),
                input_lengths.cpu().numpy().tobytes(), target_lengths.cpu().numpy().tobytes())
         if sig != self._sig:

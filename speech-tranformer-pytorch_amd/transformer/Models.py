@@ -279,7 +279,7 @@ class Transformer(nn.Module):
         return in_rows, t_rows
 
     def forward_packed(self, inputs, inputs_pos, targets, targets_pos, want_enc=False, cut_encoder=False,
-                       padded_logits=False, ce_truth=None, ignore_index=0, layouts=None):
+                       padded_logits=False, ce_truth=None, ignore_index=0, layouts=None, ce_spec=None, ce_denom=None):
         """The same computation with the logits left in the ragged layout the kernels produce:
         -> (logits [sum(targets_pos), V] fp32 (a column slice of a [*, v_pad] buffer), Rows of the target side).
         ``Rows.scatter_index(L)`` maps row r to its position b*L + t in the padded layout; trainer.TrainStep uses
@@ -303,9 +303,10 @@ class Transformer(nn.Module):
                 # (the ragged rows read their ground-truth entries through their padded positions: no gather launch)
                 # (a 1-D ce_truth is the padded [B, L] ground truth flattened, L = the target layout's rows per utterance,
                 # with spare elements behind it for rows that belong to no utterance: trainer.TrainStep's packed buckets)
+                # ce_spec / ce_denom (functional.ce_spec): the loss against a smoothed target - label smoothing - instead
                 L_gt = ce_truth.shape[1] if ce_truth.dim() == 2 else t_rows.max_len
                 logits = F_.VocabCeFn.apply(dec, self.tgt_word_proj.weight, self, ce_truth.contiguous().view(-1), ignore_index,
-                                            t_rows.scatter_index(L_gt))
+                                            t_rows.scatter_index(L_gt), ce_spec, ce_denom)
             else:
                 logits = F_.VocabFn.apply(dec, self.tgt_word_proj.weight, self, padded_logits)   # [sum(tgt_len), v_pad]
         if not padded_logits and ce_truth is None:
