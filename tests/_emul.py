@@ -68,14 +68,14 @@ def keep_qk(d, bh, nq, nk):
 
 
 def gemm(X, Y, out, bias=None, aux=None, epi=nv.EPI_BF16, x_cmajor=False, y_cmajor=False, splits=1, m=None, n=None,
-         kc=None, drop=None, delta=None, head_dim=0, stack=None, aux2=None):
+         kc=None, drop=None, delta=None, head_dim=0, stack=None, aux2=None, dtype=F32):
     if stack is not None:       # Y / bias: the first of `blocks` equally spaced blocks (st_gemm_stacked)
         blocks, y_stride, b_stride = stack
         Y = torch.as_strided(Y, (blocks, Y.shape[0], Y.shape[1]), (y_stride, Y.stride(0), 1)).reshape(-1, Y.shape[1])
         if bias is not None:
             bias = torch.as_strided(bias, (blocks, bias.shape[0]), (b_stride, 1)).reshape(-1)
-    Xl = (X.t() if x_cmajor else X).float()      # logical [M, Kc]
-    Yl = (Y.t() if y_cmajor else Y).float()      # logical [N, Kc]
+    Xl = (X.t() if x_cmajor else X).to(dtype)      # logical [M, Kc]
+    Yl = (Y.t() if y_cmajor else Y).to(dtype)      # logical [N, Kc]
     M = m if m is not None else Xl.shape[0]
     N = n if n is not None else Yl.shape[0]
     Kc = kc if kc is not None else Xl.shape[1]
@@ -92,9 +92,9 @@ def gemm(X, Y, out, bias=None, aux=None, epi=nv.EPI_BF16, x_cmajor=False, y_cmaj
         if _on(drop):
             acc = acc * keep_rc(drop, torch.arange(M), torch.arange(N), N) * drop.scale
     elif epi == nv.EPI_BF16_MASK:
-        acc = acc * (aux[:M, :N].float() > 0) * (drop.scale if _on(drop) else 1.0)
+        acc = acc * (aux[:M, :N].to(dtype) > 0) * (drop.scale if _on(drop) else 1.0)
     elif epi == nv.EPI_BF16_ADD:
-        acc = acc + aux[:M, :N].float()
+        acc = acc + aux[:M, :N].to(dtype)
     if epi == nv.EPI_F32_ATOMIC:
         out[:M, :N] += acc
     elif epi == nv.EPI_F32_ATOMIC_T:
@@ -102,25 +102,25 @@ def gemm(X, Y, out, bias=None, aux=None, epi=nv.EPI_BF16, x_cmajor=False, y_cmaj
     else:
         out[:M, :N] = acc.to(out.dtype)
         if epi == nv.EPI_BF16_DELTA:
-            o_hi = aux[:M, :N].float() + (aux2[:M, :N].float() if aux2 is not None else 0.0)
-            prod = out[:M, :N].float() * o_hi
+            o_hi = aux[:M, :N].to(dtype) + (aux2[:M, :N].to(dtype) if aux2 is not None else 0.0)
+            prod = out[:M, :N].to(dtype) * o_hi
             delta.view(N // head_dim, -1)[:, :M] = prod.view(M, N // head_dim, head_dim).sum(-1).t()
     return out
 
 
-def gemm_splitk(X, Y, out, splits, y_cmajor=False):
-    return gemm(X, Y, out, y_cmajor=y_cmajor)
+def gemm_splitk(X, Y, out, splits, y_cmajor=False, dtype=F32):
+    return gemm(X, Y, out, y_cmajor=y_cmajor, dtype=dtype)
 
 
-def gemm_kscale(X, W, out, bias, col_lo, col_hi, scale):
-    acc = X.float() @ W.float().t() + (bias.float() if bias is not None else 0.0)
+def gemm_kscale(X, W, out, bias, col_lo, col_hi, scale, dtype=F32):
+    acc = X.to(dtype) @ W.to(dtype).t() + (bias.to(dtype) if bias is not None else 0.0)
     acc[:, col_lo:col_hi] *= float(scale)
     out[:X.shape[0], :W.shape[0]] = acc.to(BF16)
     return out
 
 
-def gemm_ws(X, W, out, bias=None, relu=False, drop=None, stack=None):
-    return gemm(X, W, out, bias=bias, epi=nv.EPI_BF16_RELU if relu else nv.EPI_BF16, drop=drop, stack=stack)
+def gemm_ws(X, W, out, bias=None, relu=False, drop=None, stack=None, dtype=F32):
+    return gemm(X, W, out, bias=bias, epi=nv.EPI_BF16_RELU if relu else nv.EPI_BF16, drop=drop, stack=stack, dtype=dtype)
 
 
 def adam_clip(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale=1.0):
@@ -139,22 +139,22 @@ def wgrad_group(problems, wide=False):
 
 
 def gemm_ln(X, W, bias, res, gamma, beta, out, xhat, rstd, eps=1e-6, relu=False, pe=None, pos=None, pre=None,
-            drop=None, drop_where=0):
-    v = X.float() @ W.float().t() + bias
+            drop=None, drop_where=0, dtype=F32):
+    v = X.to(dtype) @ W.to(dtype).t() + bias.to(dtype)
     M, N = v.shape
     if relu:
         v = torch.relu(v)
     if _on(drop) and drop_where == 1:
         v = v * keep_rc(drop, torch.arange(M), torch.arange(N), N) * drop.scale
     if res is not None:
-        v = v + res.float()
+        v = v + res.to(dtype)
     mu = v.mean(-1, keepdim=True)
     var = ((v - mu) ** 2).mean(-1, keepdim=True)
     rs = torch.rsqrt(var + eps)
     h = (v - mu) * rs
-    y = h * gamma + beta
+    y = h * gamma.to(dtype) + beta.to(dtype)
     if pe is not None:
-        y = y + pe[pos.long()]
+        y = y + pe[pos.long()].to(dtype)
     if _on(drop) and drop_where == 2:
         y = y * keep_rc(drop, torch.arange(M), torch.arange(N), N) * drop.scale
     out.copy_(y.to(BF16))
@@ -203,7 +203,7 @@ def relu_bits_from(H, d_model=256):
     return out
 
 
-def row_chain(A, chain, pre=None, ffn=None, post=None, eps=1e-6, post_kscale=0.0):
+def row_chain(A, chain, pre=None, ffn=None, post=None, eps=1e-6, post_kscale=0.0, dtype=F32):
     """csrc/st_rowchain.hip as a composition of the emulated kernels it replaces (same roundings: every intermediate the
     separate kernels round to bf16 is rounded here too)."""
     blocks = list(chain.blocks)
@@ -215,21 +215,21 @@ def row_chain(A, chain, pre=None, ffn=None, post=None, eps=1e-6, post_kscale=0.0
         assert len(blocks) == 4 + 4 * (d_ff // 256) + (12 if post else 0)
         M = A.shape[0]
         out0 = torch.empty(M, 512, dtype=BF16, device=A.device) if out0 is None else out0
-        gemm_ln(A, wo, bo, R[:M], g0, be0, out0, xhat0, rstd0, eps=eps)
+        gemm_ln(A, wo, bo, R[:M], g0, be0, out0, xhat0, rstd0, eps=eps, dtype=dtype)
         H = torch.empty(M, d_ff, dtype=BF16, device=A.device) if H is None else H
-        gemm(out0, w1, H, bias=b1, epi=nv.EPI_BF16_RELU, drop=drop1)
+        gemm(out0, w1, H, bias=b1, epi=nv.EPI_BF16_RELU, drop=drop1, dtype=dtype)
         if relu_bits is not None:
-            _pack_bits(H[:M].float() > 0, relu_bits)
-        gemm_ln(H, w2, b2, out0, g1, be1, out1, xhat1, rstd1, eps=eps, drop=drop2, drop_where=2 if _on(drop2) else 0)
+            _pack_bits(H[:M].to(dtype) > 0, relu_bits)
+        gemm_ln(H, w2, b2, out0, g1, be1, out1, xhat1, rstd1, eps=eps, drop=drop2, drop_where=2 if _on(drop2) else 0, dtype=dtype)
         if post:
             nb, bp, P = post
             wp = blocks[4 + 4 * (d_ff // 256)][0]
             if post_kscale not in (0.0, 1.0):
-                acc = out1[:M].float() @ wp.float().t() + bp.float()
+                acc = out1[:M].to(dtype) @ wp.to(dtype).t() + bp.to(dtype)
                 acc[:, 512:1024] *= float(post_kscale)
                 P[:M] = acc.to(BF16)
             else:
-                gemm(out1, wp, P, bias=bp)
+                gemm(out1, wp, P, bias=bp, dtype=dtype)
         return
 
     def take(n):
@@ -243,7 +243,7 @@ def row_chain(A, chain, pre=None, ffn=None, post=None, eps=1e-6, post_kscale=0.0
         (wo,) = take(1)
         if out0 is None:
             out0 = torch.empty(A.shape[0], 256, dtype=BF16, device=A.device)
-        gemm_ln(A, wo, bo, R[:A.shape[0]], g0, be0, out0, xhat0, rstd0, eps=eps)
+        gemm_ln(A, wo, bo, R[:A.shape[0]], g0, be0, out0, xhat0, rstd0, eps=eps, dtype=dtype)
         cur = out0
     if ffn:
         relu_bits = ffn[11] if len(ffn) == 12 else None
@@ -253,24 +253,24 @@ def row_chain(A, chain, pre=None, ffn=None, post=None, eps=1e-6, post_kscale=0.0
         w2 = torch.cat(ws[1::2], 1)
         if H is None:          # inference: the hidden activation is not handed out
             H = torch.empty(A.shape[0], d_ff, dtype=BF16, device=A.device)
-        gemm(cur, w1, H, bias=b1, epi=nv.EPI_BF16_RELU, drop=drop1)
+        gemm(cur, w1, H, bias=b1, epi=nv.EPI_BF16_RELU, drop=drop1, dtype=dtype)
         if relu_bits is not None:
-            _pack_bits(H[:A.shape[0]].float() > 0, relu_bits)
-        gemm_ln(H, w2, b2, cur, g1, be1, out1, xhat1, rstd1, eps=eps, drop=drop2, drop_where=2 if _on(drop2) else 0)
+            _pack_bits(H[:A.shape[0]].to(dtype) > 0, relu_bits)
+        gemm_ln(H, w2, b2, cur, g1, be1, out1, xhat1, rstd1, eps=eps, drop=drop2, drop_where=2 if _on(drop2) else 0, dtype=dtype)
         cur = out1
     if post:
         nb, bp, P = post
         if nb == 3 and post_kscale not in (0.0, 1.0):       # the key block leaves scaled, in fp32, before its one rounding
             wp = torch.cat(take(nb), 0)
-            acc = cur[:A.shape[0]].float() @ wp.float().t() + bp.float()
+            acc = cur[:A.shape[0]].to(dtype) @ wp.to(dtype).t() + bp.to(dtype)
             acc[:, 256:512] *= float(post_kscale)
             P[:A.shape[0]] = acc.to(BF16)
         else:
-            gemm(cur, torch.cat(take(nb), 0), P, bias=bp)
+            gemm(cur, torch.cat(take(nb), 0), P, bias=bp, dtype=dtype)
     assert not blocks
 
 
-def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None):
+def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None, dtype=F32, dbias_rounded=False):
     """csrc/st_rowchain.hip's backward chain as a composition of the emulated kernels it replaces."""
     blocks = list(chain.blocks)
     if ffn is not None and ffn[4] is not None and ffn[4].shape[1] == 512:      # csrc/st_rowchain_pipe512_bwd.cuh (chains.encoder512_blocks_bwd)
@@ -280,16 +280,16 @@ def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None):
         assert all(b[3] for b in blocks) and len(blocks) == 2 * nb + 4 * (d_ff // 256) + 4
         w2, w1, wo = blocks[2 * nb][0], blocks[2 * nb + 2][0], blocks[-1][0]
         if nb:
-            gemm_lnbwd(dP[:M], blocks[0][0], None if G is None else G[:M], xa, ra[:M], ga, dsa[:M], dga, dba, dbia, drop=drop)
+            gemm_lnbwd(dP[:M], blocks[0][0], None if G is None else G[:M], xa, ra[:M], ga, dsa[:M], dga, dba, dbia, drop=drop, dtype=dtype, dbias_rounded=dbias_rounded)
         else:
-            ln_bwd(G[:M], xa[:M], ra[:M], ga, dsa[:M], dga, dba, dbia, drop=drop)
+            ln_bwd(G[:M], xa[:M], ra[:M], ga, dsa[:M], dga, dba, dbia, drop=drop, dtype=dtype, dbias_rounded=dbias_rounded)
         ds = dsa[:M]
-        acc = ds.float() @ w2.float()
-        dH[:M] = ((acc * msc).to(BF16).float() * _unpack_bits(relu_bits, M, d_ff)).to(BF16)
-        gemm_lnbwd(dH[:M], w1, ds, xb, rb[:M], gb, dsb[:M], dgb, dbb, dbib)
+        acc = ds.to(dtype) @ w2.to(dtype)
+        dH[:M] = ((acc * msc).to(BF16).to(dtype) * _unpack_bits(relu_bits, M, d_ff)).to(BF16)
+        gemm_lnbwd(dH[:M], w1, ds, xb, rb[:M], gb, dsb[:M], dgb, dbb, dbib, dtype=dtype, dbias_rounded=dbias_rounded)
         dl = torch.zeros(8 * M, dtype=torch.float32)
         out = torch.zeros(M, 512, dtype=BF16)
-        gemm(dsb[:M], wo, out, epi=nv.EPI_BF16_DELTA, aux=O[:M], aux2=None if Ores is None else Ores[:M], y_cmajor=True, delta=dl, head_dim=64)
+        gemm(dsb[:M], wo, out, epi=nv.EPI_BF16_DELTA, aux=O[:M], aux2=None if Ores is None else Ores[:M], y_cmajor=True, delta=dl, head_dim=64, dtype=dtype)
         dctx[:M] = out
         delta.view(8, -1)[:, :M] = dl.view(8, M)
         return
@@ -305,18 +305,18 @@ def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None):
         nb, dP, G, xa, ra, ga, drop, dsa, dga, dba, dbia = head
         if nb:
             wp = torch.cat(take(nb), 0)                          # [256 nb (contraction), 256]
-            gemm_lnbwd(dP[:M], wp, None if G is None else G[:M], xa, ra[:M], ga, dsa[:M], dga, dba, dbia, drop=drop)
+            gemm_lnbwd(dP[:M], wp, None if G is None else G[:M], xa, ra[:M], ga, dsa[:M], dga, dba, dbia, drop=drop, dtype=dtype, dbias_rounded=dbias_rounded)
         else:
-            ln_bwd(G[:M], xa[:M], ra[:M], ga, dsa[:M], dga, dba, dbia, drop=drop)
+            ln_bwd(G[:M], xa[:M], ra[:M], ga, dsa[:M], dga, dba, dbia, drop=drop, dtype=dtype, dbias_rounded=dbias_rounded)
         ds = dsa[:M]
     if ffn:
         d_ff, relu_bits, msc, dH, xb, rb, gb, dsb, dgb, dbb, dbib = ffn
         ws = take(2 * (d_ff // 256))
         w2 = torch.cat(ws[0::2], 1)                          # [256 (contraction), d_ff]
         w1 = torch.cat(ws[1::2], 0)                          # [d_ff (contraction), 256]
-        acc = ds.float() @ w2.float()
-        dH[:M] = ((acc * msc).to(BF16).float() * _unpack_bits(relu_bits, M, d_ff)).to(BF16)
-        gemm_lnbwd(dH[:M], w1, ds, xb, rb[:M], gb, dsb[:M], dgb, dbb, dbib)
+        acc = ds.to(dtype) @ w2.to(dtype)
+        dH[:M] = ((acc * msc).to(BF16).to(dtype) * _unpack_bits(relu_bits, M, d_ff)).to(BF16)
+        gemm_lnbwd(dH[:M], w1, ds, xb, rb[:M], gb, dsb[:M], dgb, dbb, dbib, dtype=dtype, dbias_rounded=dbias_rounded)
         ds = dsb[:M]
     if tail:
         O, Ores, dctx, delta = tail
@@ -324,45 +324,49 @@ def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None):
         dl = torch.zeros(4 * M, dtype=torch.float32)
         out = torch.zeros(M, 256, dtype=BF16)
         gemm(ds, wo, out, epi=nv.EPI_BF16_DELTA, aux=O[:M], aux2=None if Ores is None else Ores[:M], y_cmajor=True, delta=dl,
-             head_dim=64)
+             head_dim=64, dtype=dtype)
         dctx[:M] = out
         delta.view(4, -1)[:, :M] = dl.view(4, M)
     assert not blocks
 
 
-def gemm_lnbwd(dY, W, aux, xhat, rstd, gamma, dx, dgamma=None, dbeta=None, dbias=None, drop=None):
+def gemm_lnbwd(dY, W, aux, xhat, rstd, gamma, dx, dgamma=None, dbeta=None, dbias=None, drop=None, dtype=F32, dbias_rounded=False):
     dy = torch.zeros(dY.shape[0], W.shape[1], dtype=BF16)
-    gemm(dY, W, dy, aux=aux, epi=nv.EPI_BF16_ADD if aux is not None else nv.EPI_BF16, y_cmajor=True)
-    return ln_bwd(dy, xhat[:dY.shape[0]], rstd, gamma, dx, dgamma, dbeta, dbias, drop=drop)
+    gemm(dY, W, dy, aux=aux, epi=nv.EPI_BF16_ADD if aux is not None else nv.EPI_BF16, y_cmajor=True, dtype=dtype)
+    return ln_bwd(dy, xhat[:dY.shape[0]], rstd, gamma, dx, dgamma, dbeta, dbias, drop=drop, dtype=dtype, dbias_rounded=dbias_rounded)
 
 
-def ln_bwd(dy, xhat, rstd, gamma, dx, dgamma=None, dbeta=None, dbias=None, mask=None, drop=None, mask_scale=1.0):
-    d, xh = dy.float(), xhat.float()
+def ln_bwd(dy, xhat, rstd, gamma, dx, dgamma=None, dbeta=None, dbias=None, mask=None, drop=None, mask_scale=1.0, dtype=F32,
+           dbias_rounded=False):
+    """dbias_rounded: the bias gradient is the column sum of dx AS STORED (bf16) - what st_gemm_lnbwd and the backward row chains
+    add up, from the 256-byte row segments they store; st_ln_bwd sums the fp32 values before their rounding.  The kernel tests ask
+    gemm_lnbwd / row_chain_bwd for it; the composition tests keep one form throughout (they compare the emulation with itself)."""
+    d, xh = dy.to(dtype), xhat.to(dtype)
     if _on(drop):
         d = d * keep_rc(drop, torch.arange(d.shape[0]), torch.arange(d.shape[1]), d.shape[1]) * drop.scale
-    g = d * gamma
-    v = rstd.unsqueeze(-1) * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
+    g = d * gamma.to(dtype)
+    v = rstd.to(dtype).unsqueeze(-1) * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
     if mask is not None:
-        v = v * (mask.float() > 0) * mask_scale
+        v = v * (mask.to(dtype) > 0) * mask_scale
     dx.copy_(v.to(BF16))
     if dgamma is not None:
         dgamma += (d * xh).sum(0)
     if dbeta is not None:
         dbeta += d.sum(0)
     if dbias is not None:
-        dbias += v.sum(0)
+        dbias += dx.to(dtype).sum(0) if dbias_rounded else v.sum(0)
     return dx
 
 
-def _attn_core(Q, K, V, q_off, q_len, k_off, k_len, H, causal, scale, b, h, k_prescaled=False):
+def _attn_core(Q, K, V, q_off, q_len, k_off, k_len, H, causal, scale, b, h, k_prescaled=False, dtype=F32):
     dk = Q.shape[1] // H
     qo, ql, ko, kl = int(q_off[b]), int(q_len[b]), int(k_off[b]), int(k_len[b])
     cs = slice(h * dk, (h + 1) * dk)
-    q = Q[qo:qo + ql, cs].float()
-    k = K[ko:ko + kl, cs].float()
+    q = Q[qo:qo + ql, cs].to(dtype)
+    k = K[ko:ko + kl, cs].to(dtype)
     if k_prescaled:       # K holds scale * log2(e) * k: the emulation works on k (the kernels never undo the scale - they skip theirs)
         k = k / (scale * nv.K_LOG2_SCALE)
-    v = V[ko:ko + kl, cs].float()
+    v = V[ko:ko + kl, cs].to(dtype)
     s = q @ k.t() * scale
     if causal:
         s = s.masked_fill(torch.ones(ql, kl, dtype=torch.bool).triu(1), float("-inf"))
@@ -370,28 +374,28 @@ def _attn_core(Q, K, V, q_off, q_len, k_off, k_len, H, causal, scale, b, h, k_pr
 
 
 def attn_fwd(Q, K, V, O, lse, q_off, q_len, k_off, k_len, n_head, max_q, causal, scale, work=None, drop=None,
-             max_k=0, ores=None, k_prescaled=False):
+             max_k=0, ores=None, k_prescaled=False, dtype=F32):
     rows = Q.shape[0]
     for b in range(q_off.numel()):
         for h in range(n_head):
-            q, k, v, s, qs, ks, cs = _attn_core(Q, K, V, q_off, q_len, k_off, k_len, n_head, causal, scale, b, h, k_prescaled)
+            q, k, v, s, qs, ks, cs = _attn_core(Q, K, V, q_off, q_len, k_off, k_len, n_head, causal, scale, b, h, k_prescaled, dtype)
             p = torch.softmax(s, -1)
             if _on(drop):   # the kernel drops un-normalised weights and folds 1/(1-p) into the final 1/l
                 p = p * keep_qk(drop, b * n_head + h, *s.shape)
-                o32 = p.to(BF16).float() @ v * drop.scale
+                o32 = p.to(BF16).to(dtype) @ v * drop.scale
                 O[qs, cs] = o32.to(BF16)
                 if ores is not None:
-                    ores[qs, cs] = (o32 - O[qs, cs].float()).to(BF16)
+                    ores[qs, cs] = (o32 - O[qs, cs].to(dtype)).to(BF16)
                 lse.view(n_head, rows)[h, qs] = torch.logsumexp(s, -1) / math.log(2.0)
                 continue
             if ores is not None and max_q <= 64:     # the kernel's psplit mode: P as hi + lo bf16 terms
-                hi = p.to(BF16).float()
-                o32 = (hi + (p - hi).to(BF16).float()) @ v
+                hi = p.to(BF16).to(dtype)
+                o32 = (hi + (p - hi).to(BF16).to(dtype)) @ v
             else:
-                o32 = p.to(BF16).float() @ v
+                o32 = p.to(BF16).to(dtype) @ v
             O[qs, cs] = o32.to(BF16)
             if ores is not None:
-                ores[qs, cs] = (o32 - O[qs, cs].float()).to(BF16)
+                ores[qs, cs] = (o32 - O[qs, cs].to(dtype)).to(BF16)
             lse.view(n_head, rows)[h, qs] = torch.logsumexp(s, -1) / math.log(2.0)
     return O
 
@@ -415,27 +419,27 @@ def attn_sf1_fwd(qkv, Os, lses, pre, post, chain, K, V, O, lse, q_off, q_len, k_
 
 
 def attn_bwd(Q, K, V, O, dO, lse, delta, dQ, dK, dV, q_off, q_len, k_off, k_len, n_head, max_q, max_k, causal, scale,
-             parts=3, work_q=None, work_k=None, drop=None, k_prescaled=False):
+             parts=3, work_q=None, work_k=None, drop=None, k_prescaled=False, dtype=F32):
     rows = Q.shape[0]
     for b in range(q_off.numel()):
         for h in range(n_head):
-            q, k, v, s, qs, ks, cs = _attn_core(Q, K, V, q_off, q_len, k_off, k_len, n_head, causal, scale, b, h, k_prescaled)
-            p = torch.exp2(s / math.log(2.0) - lse.view(n_head, rows)[h, qs].unsqueeze(-1))
-            do = dO[qs, cs].float()
+            q, k, v, s, qs, ks, cs = _attn_core(Q, K, V, q_off, q_len, k_off, k_len, n_head, causal, scale, b, h, k_prescaled, dtype)
+            p = torch.exp2(s / math.log(2.0) - lse.view(n_head, rows)[h, qs].to(dtype).unsqueeze(-1))
+            do = dO[qs, cs].to(dtype)
             if O is not None:
-                dl = (do * O[qs, cs].float()).sum(-1, keepdim=True)
+                dl = (do * O[qs, cs].to(dtype)).sum(-1, keepdim=True)
                 delta.view(n_head, rows)[h, qs] = dl.squeeze(-1)
             else:
-                dl = delta.view(n_head, rows)[h, qs].unsqueeze(-1)
+                dl = delta.view(n_head, rows)[h, qs].to(dtype).unsqueeze(-1)
             dp = do @ v.t()
             pv = p
             if _on(drop):
                 keep = keep_qk(drop, b * n_head + h, *s.shape) * drop.scale
                 dp, pv = dp * keep, p * keep
-            ds = (p * (dp - dl)).to(BF16).float()
+            ds = (p * (dp - dl)).to(BF16).to(dtype)
             dQ[qs, cs] = (ds @ k * scale).to(BF16)
             dK[ks, cs] = (ds.t() @ q * scale).to(BF16)
-            dV[ks, cs] = (pv.to(BF16).float().t() @ do).to(BF16)
+            dV[ks, cs] = (pv.to(BF16).to(dtype).t() @ do).to(BF16)
 
 
 def _dense_core(Q, K, V, mask, b, h, n_head, Lq, Lk, scale, drop):
@@ -489,12 +493,12 @@ def ctc_gather(logits, rowmap, T, cols, lse, lp, V=None):
     lp.view(-1, lp.shape[2])[rowmap[ok]] = logits[rows.view(-1, 1), cols[b].long()] - l[rows].view(-1, 1)
 
 
-def ctc_dlogits(logits, lse, rowmap, T, roww, scat, gsmall, grad_out, dlogits, V=None):
+def ctc_dlogits(logits, lse, rowmap, T, roww, scat, gsmall, grad_out, dlogits, V=None, dtype=F32):
     V = logits.shape[1] if V is None else V
     ok = rowmap >= 0
     b = torch.div(rowmap.clamp_min(0), T, rounding_mode="floor")
     w = torch.where(ok, roww[b], torch.zeros_like(lse)) * grad_out.reshape(())
-    dense = torch.exp(logits[:, :V].float() - lse.view(-1, 1)) * w.view(-1, 1)
+    dense = torch.exp(logits[:, :V].to(dtype) - lse.to(dtype).view(-1, 1)) * w.to(dtype).view(-1, 1)
     dlogits.zero_()
     dlogits[:, :V] = dense.to(BF16)
     g = gsmall.view(-1, gsmall.shape[2])
@@ -504,15 +508,15 @@ def ctc_dlogits(logits, lse, rowmap, T, roww, scat, gsmall, grad_out, dlogits, V
         dlogits[r, sc[keep].long()] = (g[int(rowmap[r])][keep] * grad_out.reshape(())).to(BF16)
 
 
-def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False):
+def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False, dtype=F32):
     B = q_off.numel()
     d_k = Q.shape[1] // n_head
-    P = torch.zeros(B, n_head, int(Lq), int(Lk))
+    P = torch.zeros(B, n_head, int(Lq), int(Lk), dtype=dtype)
     for b in range(B):
         lq, lk, qo, ko = int(q_len[b]), int(k_len[b]), int(q_off[b]), int(k_off[b])
         for h in range(n_head):
-            q = Q[qo:qo + lq, h * d_k:(h + 1) * d_k].float()
-            k = K[ko:ko + lk, h * d_k:(h + 1) * d_k].float()
+            q = Q[qo:qo + lq, h * d_k:(h + 1) * d_k].to(dtype)
+            k = K[ko:ko + lk, h * d_k:(h + 1) * d_k].to(dtype)
             s = q @ k.t() * (math.log(2.0) if k_prescaled else scale)
             if causal:
                 s = s.masked_fill(torch.ones(lq, lk, dtype=torch.bool).triu(1), float("-inf"))
@@ -594,7 +598,7 @@ def embed_step(tokens, emb, pe, step, out):
     return out
 
 
-def decode_self_attn(qkv, cache, step, ctx, n_head, scale, anc=None):
+def decode_self_attn(qkv, cache, step, ctx, n_head, scale, anc=None, dtype=F32):
     n, S, w = cache.shape
     d = w // 2
     t = int(step)
@@ -604,9 +608,9 @@ def decode_self_attn(qkv, cache, step, ctx, n_head, scale, anc=None):
         rows = anc[:, :t + 1].long().clone()
         rows[:, t] = torch.arange(n)
         hist = cache[rows, torch.arange(t + 1).unsqueeze(0).expand(n, t + 1)]
-    k = hist[:, :, :d].float().view(n, t + 1, n_head, d // n_head)
-    v = hist[:, :, d:].float().view(n, t + 1, n_head, d // n_head)
-    q = qkv[:, :d].float().view(n, 1, n_head, d // n_head)
+    k = hist[:, :, :d].to(dtype).view(n, t + 1, n_head, d // n_head)
+    v = hist[:, :, d:].to(dtype).view(n, t + 1, n_head, d // n_head)
+    q = qkv[:, :d].to(dtype).view(n, 1, n_head, d // n_head)
     sc = (q * k).sum(-1) * scale                         # [n, t + 1, H]
     p = torch.softmax(sc, dim=1).unsqueeze(-1)
     ctx.copy_((p * v).sum(1).reshape(n, d).to(BF16))
@@ -661,14 +665,14 @@ def ce_fwd(logits, target, ignore_index, lse, sums, V=None, index=None):
     sums[2] = sums[0] / sums[1]
 
 
-def ce_bwd(logits, target, ignore_index, lse, sums, grad_out, dlogits, V=None, index=None):
+def ce_bwd(logits, target, ignore_index, lse, sums, grad_out, dlogits, V=None, index=None, dtype=F32):
     V = logits.shape[1] if V is None else V
     target = target if index is None else target.reshape(-1)[index]
-    valid = (target != ignore_index).float().view(-1, 1)
-    g = torch.exp(logits[:, :V].float() - lse.view(-1, 1))
-    g.scatter_add_(1, target.clamp(0, V - 1).view(-1, 1), -torch.ones(len(target), 1))
+    valid = (target != ignore_index).to(dtype).view(-1, 1)
+    g = torch.exp(logits[:, :V].to(dtype) - lse.to(dtype).view(-1, 1))
+    g.scatter_add_(1, target.clamp(0, V - 1).view(-1, 1), -torch.ones(len(target), 1, dtype=dtype))
     dlogits.zero_()
-    dlogits[:, :V] = (g * valid * (grad_out.float() / sums[1])).to(BF16)
+    dlogits[:, :V] = (g * valid * (grad_out.to(dtype) / sums[1])).to(BF16)
 
 
 def zero_tails(table, n_max):

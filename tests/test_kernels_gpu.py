@@ -6,6 +6,7 @@ Tolerances: operands are bf16 on both sides, accumulation is fp32 on both
 sides, so differences come from accumulation order and one bf16 rounding of the
 result: rel-L2 <= 1e-2 for bf16 outputs, <= 2e-3 for fp32 outputs / reductions.
 """
+import functools
 import math
 import os
 
@@ -14,25 +15,57 @@ import torch
 
 from st_amd import native as nv
 from tests import _emul as em
+from tests._local import Guarded, check, check_local, guarded_input, rel  # noqa: F401  (check / rel: also imported from here by other test files)
 
 pytestmark = pytest.mark.gpu
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+# The local bounds (every row, every column, every element of an fp32 vector on its own: tests/_local.py) and where they come
+# from: tests/LOCAL_BOUNDS.md.  None is tuned against a kernel.
+L_BF16 = 1e-2                     # single-rounding bf16 outputs (GEMM family, row-chain outputs, pack / embed / cast): one bf16 ulp <= 2^-7 of a row's norm
+L_F32 = 2e-3                      # fp32 GEMM outputs, rstd, lse, delta: 3 x the emulation's fp32-vs-fp64 figure is far below the family's 2e-3
+L_LNBWD = dict(dx=1e-2, dgamma=3e-3, dbeta=3e-3, dbias=5e-3)             # st_ln_bwd: the family's global tolerances (3 x measured is below each)
+L_GEMM_LNBWD = dict(dx=1.5e-2, dgamma=5e-3, dbeta=5e-3, dbias=8e-3)       # st_gemm_lnbwd, likewise
+# attention: likewise.  delta = rowsum(dO * O) is a function of the backward's INPUTS dO and O: its reference is that sum, in fp64, over the
+# O the kernel was handed (_delta_of) - an fp32 sum of d_k products, 3 x measured 1e-6, held to the fp32 vectors' 2e-3
+L_ATTN = dict(O=1.5e-2, lse=2e-3, dQ=2.5e-2, dK=2.5e-2, dV=2e-2, delta=2e-3)
+L_ATTN_DROP = dict(O=2e-2, lse=2e-3, dQ=3e-2, dK=3e-2, dV=2.5e-2, delta=2e-3)         # ... with dropout on the probabilities
+# st_row_chain_bwd / st_row_chain512_bwd: every stage reads the bf16 output of the one before, so a rounding that flips upstream moves
+# everything downstream - most of all delta, a sum of 64 products of such values: 3 x the measured figure where that exceeds the family's
+# 1e-2 (bf16) / 5e-3 (fp32), those otherwise
+L_CHAIN_BWD = dict(ds_a=1e-2, dH=1e-2, ds_b=1e-2, dctx=1.3e-2, delta=0.17, dga=5e-3, dba=5e-3, dbia=5e-3, dgb=5e-3, dbb=5e-3, dbib=5.3e-3)
+L_CHAIN512_BWD = dict(ds_a=1e-2, dH=1e-2, ds_b=1e-2, dctx=1.1e-2, delta=0.14, dga=5e-3, dba=5e-3, dbia=5e-3, dgb=1.6e-2, dbb=8.5e-3, dbib=1.05e-2)
+L_CE = 6e-3                       # st_ce_bwd's bf16 gradient
+L_PROBS = 1e-4                    # st_attn_probs' fp32 maps, row by row: the family's tolerance against the emulation
 
 
-def check(got, ref, tol, what):
-    got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
-    assert torch.isfinite(got).all(), "%s: non-finite output" % what
-    r = rel(got, ref)
-    if r > tol:
-        err = (got - ref).abs()
-        idx = torch.nonzero(err == err.max())[0].tolist()
-        raise AssertionError("%s: rel-L2 %.3e > %.1e; max |err| %.4g at %s (got %.5g, ref %.5g)"
-                             % (what, r, tol, err.max().item(), idx, got[tuple(idx)].item(), ref[tuple(idx)].item()))
+def GO(rows, cols, dtype=BF16, contiguous=False, **kw):
+    """A guarded output on the GPU: NaN (integers: a fixed pattern) everywhere, the window included; ``contiguous``: row guards only, for
+    outputs whose wrapper fixes the leading dimension."""
+    return Guarded(rows, cols, dtype, "cuda", pad_cols=(0, 0) if contiguous else (64, 64), **kw)
+
+
+def GV(n, dtype=F32, **kw):
+    return Guarded.vec(n, dtype, "cuda", **kw)
+
+
+def GI(t, **kw):
+    """An operand on the GPU as a strided view whose surroundings are NaN."""
+    return None if t is None else guarded_input(t, "cuda", **kw)
+
+
+def same_bits(a, b):
+    """torch.equal for buffers that may hold the guards' NaN fill in places no kernel writes."""
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+
+
+def utt_rows(off, lens, total):
+    """bool [total]: the rows that belong to an utterance (padded layouts leave the others to nobody)."""
+    m = torch.zeros(total, dtype=torch.bool)
+    for o, n in zip(off.tolist(), lens.tolist()):
+        m[o:o + n] = True
+    return m
 
 
 def g(*shape, seed=0, scale=1.0, dtype=BF16):
@@ -78,8 +111,11 @@ def test_gemm_forward(M, N, K, epi):
     X, W, b = g(M, K, seed=1), g(N, K, seed=2, scale=K ** -0.5), g(N, seed=3, dtype=F32)
     odt = F32 if epi == nv.EPI_F32 else BF16
     ref = em.gemm(X, W, torch.zeros(M, N, dtype=odt), bias=b, epi=epi)
-    out = nv.gemm(cu(X), cu(W), torch.full((M, N), float("nan"), dtype=odt, device="cuda"), bias=cu(b), epi=epi)
-    check(out, ref, 2e-3 if epi == nv.EPI_F32 else 1e-2, "gemm fwd %s epi %d" % ((M, N, K), epi))
+    gd = GO(M, N, odt)
+    out = nv.gemm(GI(X), GI(W), gd.view, bias=cu(b), epi=epi)
+    what = "gemm fwd %s epi %d" % ((M, N, K), epi)
+    check(out, ref, 2e-3 if epi == nv.EPI_F32 else 1e-2, what, tol_local=L_F32 if epi == nv.EPI_F32 else L_BF16)
+    gd.assert_intact(what)
 
 
 def test_gemm_strided_operands():
@@ -91,8 +127,13 @@ def test_gemm_strided_operands():
     ref = em.gemm(big[:, d:2 * d], W, outbig.clone()[:, d:], bias=None)
     ob = cu(outbig)
     nv.gemm(cu(big)[:, d:2 * d], cu(W), ob[:, d:])
-    check(ob[:, d:], ref, 1e-2, "gemm strided")
+    check(ob[:, d:], ref, 1e-2, "gemm strided", tol_local=L_BF16)
     assert ob[:, :d].abs().max().item() == 0
+    # ... and with NaN instead of neighbours: the operand's surroundings must not reach the product, the output's must stay as they are
+    gd = GO(M, d)
+    nv.gemm(GI(big[:, d:2 * d]), GI(W), gd.view)
+    check(gd.view, ref, 1e-2, "gemm strided, guarded", tol_local=L_BF16)
+    gd.assert_intact("gemm strided, guarded")
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 128), (1000, 256, 1024), (333, 768, 256), (64, 4344, 256), (1206, 4344, 256)])
@@ -102,9 +143,10 @@ def test_gemm_dgrad(M, N, K, epi):
     dy, W = g(M, N, seed=1), g(N, K, seed=2, scale=N ** -0.5)
     aux = g(M, K, seed=3) if epi != nv.EPI_BF16 else None
     ref = em.gemm(dy, W, torch.zeros(M, K, dtype=BF16), aux=aux, epi=epi, y_cmajor=True)
-    out = nv.gemm(cu(dy), cu(W), torch.full((M, K), float("nan"), dtype=BF16, device="cuda"), aux=cu(aux), epi=epi,
-                  y_cmajor=True)
-    check(out, ref, 1e-2, "gemm dgrad %s epi %d" % ((M, N, K), epi))
+    gd = GO(M, K)
+    out = nv.gemm(GI(dy), GI(W), gd.view, aux=GI(aux), epi=epi, y_cmajor=True)
+    check(out, ref, 1e-2, "gemm dgrad %s epi %d" % ((M, N, K), epi), tol_local=L_BF16)
+    gd.assert_intact("gemm dgrad %s epi %d" % ((M, N, K), epi))
 
 
 @pytest.mark.parametrize("M,N,K,splits", [(256, 128, 128, 1), (1000, 256, 256, 4), (5000, 768, 256, 16),
@@ -115,20 +157,30 @@ def test_gemm_wgrad(M, N, K, splits):
     dy, x = g(M, N, seed=1), g(M, K, seed=2)
     init = g(N, K, seed=3, dtype=F32)
     ref = em.gemm(dy, x, init.clone(), epi=nv.EPI_F32_ATOMIC, x_cmajor=True, y_cmajor=True, m=N)
-    out = nv.gemm(cu(dy), cu(x), cu(init.clone()), epi=nv.EPI_F32_ATOMIC, x_cmajor=True, y_cmajor=True, splits=splits,
-                  m=N)
-    check(out, ref, 2e-3, "gemm wgrad %s" % ((M, N, K, splits),))
+    def acc():          # the accumulator inside its guards, holding the gradient already there
+        gd = GO(N, K, F32)
+        gd.view.copy_(init)
+        return gd
+
+    what = "gemm wgrad %s" % ((M, N, K, splits),)
+    gd = acc()
+    out = nv.gemm(GI(dy), GI(x), gd.view, epi=nv.EPI_F32_ATOMIC, x_cmajor=True, y_cmajor=True, splits=splits, m=N)
+    check(out, ref, 2e-3, what, tol_local=L_F32)
+    gd.assert_intact(what)
     # the production form: lane axis = k, transposed (coalesced) atomic store
-    out_t = nv.gemm(cu(x), cu(dy), cu(init.clone()), epi=nv.EPI_F32_ATOMIC_T, x_cmajor=True, y_cmajor=True,
-                    splits=splits, n=N)
-    check(out_t, ref, 2e-3, "gemm wgrad (transposed store) %s" % ((M, N, K, splits),))
+    gd = acc()
+    out_t = nv.gemm(GI(x), GI(dy), gd.view, epi=nv.EPI_F32_ATOMIC_T, x_cmajor=True, y_cmajor=True, splits=splits, n=N)
+    check(out_t, ref, 2e-3, "gemm wgrad (transposed store) %s" % ((M, N, K, splits),), tol_local=L_F32)
+    gd.assert_intact(what + " (transposed store)")
     # ... which can also accumulate the bias gradient (column sums of dy)
     b0 = g(1, N, seed=4, dtype=F32).view(-1)
-    db = cu(b0.clone())
-    out_b = nv.gemm(cu(x), cu(dy), cu(init.clone()), bias=db, epi=nv.EPI_F32_ATOMIC_T, x_cmajor=True, y_cmajor=True,
-                    splits=splits, n=N)
-    check(out_b, ref, 2e-3, "gemm wgrad + bias grad %s" % ((M, N, K, splits),))
-    check(db, b0 + dy.float().sum(0), 2e-3, "fused bias grad %s" % ((M, N, K, splits),))
+    gb = GV(N)
+    gb.view.copy_(b0)
+    gd = acc()
+    out_b = nv.gemm(cu(x), cu(dy), gd.view, bias=gb.view, epi=nv.EPI_F32_ATOMIC_T, x_cmajor=True, y_cmajor=True, splits=splits, n=N)
+    check(out_b, ref, 2e-3, "gemm wgrad + bias grad %s" % ((M, N, K, splits),), tol_local=L_F32)
+    check(gb.view, b0 + dy.float().sum(0), 2e-3, "fused bias grad %s" % ((M, N, K, splits),), tol_local=L_F32)
+    gd.assert_intact(what + " + bias grad"), gb.assert_intact(what + ": bias grad")
 
 
 @pytest.mark.parametrize("M,N,K", [(300, 128, 128), (1000, 256, 256), (130, 256, 1024), (70, 512, 512), (500, 256, 80),
@@ -146,16 +198,24 @@ def test_gemm_ln(M, N, K, variant):
 
     def run(fn, dev):
         mv = (lambda t: None if t is None else t.to(dev))
-        out, xhat, pre = (torch.zeros(M, N, dtype=BF16, device=dev) for _ in range(3))
-        rstd = torch.zeros(M, dtype=F32, device=dev)
-        fn(mv(X), mv(W), mv(b), mv(res), mv(gamma), mv(beta), out, xhat, rstd, eps=1e-6, relu=relu, pe=mv(pe),
+        op = mv
+        if dev == "cuda":       # out takes any leading dimension; xhat / pre are [M, N] exactly (row guards); strided operands in NaN
+            gds.extend([GO(M, N), GO(M, N, contiguous=True), GV(M), GO(M, N, contiguous=True)])
+            out, xhat, rstd, pre = (gd.view for gd in gds)
+            op = GI
+        else:
+            out, xhat, pre = (torch.zeros(M, N, dtype=BF16) for _ in range(3))
+            rstd = torch.zeros(M, dtype=F32)
+        fn(op(X), mv(W), mv(b), op(res), mv(gamma), mv(beta), out, xhat, rstd, eps=1e-6, relu=relu, pe=mv(pe),
            pos=mv(pos), pre=pre)
         return out, xhat, rstd, pre
 
+    gds = []
     r = run(em.gemm_ln, "cpu")
     o = run(nv.gemm_ln, "cuda")
-    for got, ref, nm, tol in zip(o, r, ("out", "xhat", "rstd", "pre"), (1e-2, 1e-2, 2e-3, 1e-2)):
-        check(got, ref, tol, "gemm_ln %s %s %s" % ((M, N, K), variant, nm))
+    for got, ref, nm, tol, gd in zip(o, r, ("out", "xhat", "rstd", "pre"), (1e-2, 1e-2, 2e-3, 1e-2), gds):
+        check(got, ref, tol, "gemm_ln %s %s %s" % ((M, N, K), variant, nm), tol_local=L_F32 if nm == "rstd" else L_BF16)
+        gd.assert_intact("gemm_ln %s %s %s" % ((M, N, K), variant, nm))
 
 
 @pytest.mark.parametrize("M,N", [(100, 128), (1000, 256), (333, 512), (5000, 256)])
@@ -167,14 +227,22 @@ def test_ln_bwd(M, N, masked):
 
     def run(fn, dev):
         mv = (lambda t: None if t is None else t.to(dev))
-        dx = torch.zeros(M, N, dtype=BF16, device=dev)
-        acc = [torch.ones(N, dtype=F32, device=dev) for _ in range(3)]   # accumulate semantics
+        if dev == "cuda":
+            gds.extend([GO(M, N)] + [GV(N) for _ in range(3)])
+            for gd in gds[1:]:
+                gd.view.fill_(1.0)                                       # accumulate semantics
+            dx, acc = gds[0].view, [gd.view for gd in gds[1:]]
+        else:
+            dx = torch.zeros(M, N, dtype=BF16, device=dev)
+            acc = [torch.ones(N, dtype=F32, device=dev) for _ in range(3)]   # accumulate semantics
         fn(mv(dy), mv(xhat), mv(rstd), mv(gamma), dx, acc[0], acc[1], acc[2], mask=mv(mask))
         return [dx] + acc
 
+    gds = []
     r, o = run(em.ln_bwd, "cpu"), run(nv.ln_bwd, "cuda")
-    for got, ref, nm, tol in zip(o, r, ("dx", "dgamma", "dbeta", "dbias"), (1e-2, 3e-3, 3e-3, 5e-3)):
-        check(got, ref, tol, "ln_bwd %s masked=%s %s" % ((M, N), masked, nm))
+    for got, ref, nm, tol, gd in zip(o, r, ("dx", "dgamma", "dbeta", "dbias"), (1e-2, 3e-3, 3e-3, 5e-3), gds):
+        check(got, ref, tol, "ln_bwd %s masked=%s %s" % ((M, N), masked, nm), tol_local=L_LNBWD[nm])
+        gd.assert_intact("ln_bwd %s masked=%s %s" % ((M, N), masked, nm))
 
 
 # ---- attention ---------------------------------------------------------------------------
@@ -201,6 +269,42 @@ def _attn_case(B, H, dk, q_lens, k_lens, causal, packed, seed):
     dO = g(Mq, d, seed=seed + 2)
     return dict(Q=Q, K=K, V=V, dO=dO, q_off=ti(q_off), q_len=ti(ql), k_off=ti(k_off), k_len=ti(k_lens), H=H,
                 max_q=max(ql), max_k=max(k_lens), causal=causal, scale=1 / math.sqrt(dk), Mq=Mq, Mk=Mk, d=d)
+
+
+def _attn_guards(c):
+    """O, lse, delta, dQ, dK, dV of an attention problem inside guards (the wrappers take any leading dimension)."""
+    return dict(O=GO(c["Mq"], c["d"]), lse=GV(c["H"] * c["Mq"]), delta=GV(c["H"] * c["Mq"]), dQ=GO(c["Mq"], c["d"]), dK=GO(c["Mk"], c["d"]),
+                dV=GO(c["Mk"], c["d"]))
+
+
+def _delta_of(dO, O, H):
+    """delta [H, rows] = rowsum over each head's columns of dO * O, in fp64 (rows of no utterance: whatever O holds there - not compared)."""
+    rows = O.shape[0]
+    return (dO.detach().double().cpu() * O.detach().double().cpu()).view(rows, H, -1).sum(-1).t().reshape(-1)
+
+
+def _attn_rows(c, nm):
+    side = "q" if nm in ("O", "lse", "dQ", "delta") else "k"
+    return utt_rows(c[side + "_off"], c[side + "_len"], c["Mq"] if side == "q" else c["Mk"])
+
+
+def check_attn(gd, got, ref, c, nm, tol, tol_local, what):
+    """One attention output against its reference on the rows that belong to an utterance (packed layouts: all of them); the rows
+    between the utterances of a padded layout belong to nobody and the kernels never write them: still the guards' fill, bit for
+    bit, like everything around the window.  lse / delta are [H, rows] vectors, judged element by element."""
+    rows = _attn_rows(c, nm)
+    got, ref = got.detach().cpu(), ref.detach().cpu()
+    if got.dim() == 1:
+        g2, r2 = got.view(c["H"], -1), ref.view(c["H"], -1)
+        check(g2[:, rows].reshape(-1), r2[:, rows].reshape(-1), tol, what, tol_local=tol_local)
+        if gd is not None:
+            assert bool(torch.isnan(g2[:, ~rows]).all()), "%s: an entry of a row that belongs to no utterance was written" % what
+    else:
+        check(got[rows], ref[rows], tol, what, tol_local=tol_local)
+        if gd is not None and not bool(rows.all()):
+            gd.assert_untouched(~rows, what)
+    if gd is not None:
+        gd.assert_intact(what)
 
 
 ATTN_CASES = [
@@ -233,18 +337,26 @@ def test_attention_fwd_bwd(case):
         meta = [mv(c[k]) for k in ("q_off", "q_len", "k_off", "k_len")]
         O = torch.zeros(c["Mq"], c["d"], dtype=BF16, device=dev)
         lse = torch.zeros(c["H"] * c["Mq"], dtype=F32, device=dev)
-        fwd(Q, K, V, O, lse, *meta, c["H"], c["max_q"], c["causal"], c["scale"], max_k=c["max_k"])
-        delta = torch.zeros_like(lse)
         dQ = torch.zeros(c["Mq"], c["d"], dtype=BF16, device=dev)
         dK, dV = (torch.zeros(c["Mk"], c["d"], dtype=BF16, device=dev) for _ in range(2))
+        delta = torch.zeros_like(lse)
+        if dev == "cuda":
+            gd.update(_attn_guards(c))
+            O, lse, dQ, dK, dV, delta = (gd[n].view for n in ("O", "lse", "dQ", "dK", "dV", "delta"))
+        fwd(Q, K, V, O, lse, *meta, c["H"], c["max_q"], c["causal"], c["scale"], max_k=c["max_k"])
         bwd(Q, K, V, O, dO, lse, delta, dQ, dK, dV, *meta, c["H"], c["max_q"], c["max_k"], c["causal"], c["scale"])
-        return O, lse, dQ, dK, dV
+        return O, lse, dQ, dK, dV, delta
 
+    gd = {}
     r = run(em.attn_fwd, em.attn_bwd, "cpu")
     o = run(nv.attn_fwd, nv.attn_bwd, "cuda")
-    # rows outside every utterance (padded layout) are untouched zeros on both sides
+    # rows outside every utterance (padded layout) are never written: still the guards' fill
     for got, ref, nm, tol in zip(o, r, ("O", "lse", "dQ", "dK", "dV"), (1.5e-2, 2e-3, 2.5e-2, 2.5e-2, 2e-2)):
-        check(got, ref, tol, "attention %s %s" % (case, nm))
+        check_attn(gd[nm], got, ref, c, nm, tol, L_ATTN[nm], "attention %s %s" % (case, nm))
+    # delta, which the dQ kernel writes for the dK / dV kernel: rowsum(dO * O) over the O it read, entry by entry; and the emulation's own
+    # delta (from ITS O, a bf16 rounding away) as a whole vector, at O's tolerance - delta is linear in O
+    check_attn(gd["delta"], o[5], _delta_of(c["dO"], o[0], c["H"]), c, "delta", 2e-3, L_ATTN["delta"], "attention %s delta" % (case,))
+    check_attn(None, o[5], r[5], c, "delta", 1.5e-2, None, "attention %s delta vs the emulation's" % (case,))
 
 
 # delta supplied by the producer of dO (O = None): ONE launch for dQ and dK/dV - the form the training step uses.  Long non-causal
@@ -434,15 +546,12 @@ def test_attention_bwd_delta_supplied(case, use_work):
         q_rows = Rows.packed(c["q_len"].long(), "cuda")
         k_rows = q_rows if case[3] is None else Rows.packed(c["k_len"].long(), "cuda")
         _, wq, wk = attn_work(q_rows, k_rows, c["causal"], dk, H)
-    got = [torch.full((Mq, c["d"]), float("nan"), dtype=BF16, device="cuda")] + \
-          [torch.full((c["Mk"], c["d"]), float("nan"), dtype=BF16, device="cuda") for _ in range(2)]
+    gd = _attn_guards(c)
+    got = [gd[n].view for n in ("dQ", "dK", "dV")]
     nv.attn_bwd(cu(c["Q"]), cu(c["K"]), cu(c["V"]), None, cu(c["dO"]), cu(lse), cu(delta), *got, *[cu(m) for m in meta_c], H, c["max_q"],
                 c["max_k"], c["causal"], c["scale"], work_q=wq, work_k=wk)
-    for g_, r_, nm, tol, off, ln in zip(got, ref, ("dQ", "dK", "dV"), (2.5e-2, 2.5e-2, 2e-2), ("q_off", "k_off", "k_off"),
-                                        ("q_len", "k_len", "k_len")):
-        rows = torch.cat([torch.arange(int(o), int(o) + int(n)) for o, n in zip(c[off], c[ln])])      # utterance rows (padded layout: the rest is untouched)
-        assert torch.isfinite(g_.float().cpu()[rows]).all(), "non-finite %s %s" % (nm, case)
-        check(g_.cpu()[rows], r_[rows], tol, "attention (delta supplied) %s %s" % (case, nm))
+    for g_, r_, nm, tol in zip(got, ref, ("dQ", "dK", "dV"), (2.5e-2, 2.5e-2, 2e-2)):      # utterance rows (padded layout: the rest is untouched)
+        check_attn(gd[nm], g_, r_, c, nm, tol, L_ATTN[nm], "attention (delta supplied) %s %s" % (case, nm))
 
 
 # Pre-scaled keys (round 5): K~ = bf16(scale * log2(e) * k), scaled in the fp32 epilogue of the projection that produced the keys
@@ -474,19 +583,16 @@ def test_attention_prescaled_keys(case):
     em.attn_bwd(c["Q"], kt, c["V"], None, c["dO"], lse, delta, *ref, *meta_c, H, c["max_q"], c["max_k"], c["causal"], c["scale"],
                 k_prescaled=True)
     meta = [cu(m) for m in meta_c]
-    Og, lseg = torch.zeros(Mq, d, dtype=BF16, device="cuda"), torch.zeros(H * Mq, dtype=F32, device="cuda")
+    gd = _attn_guards(c)
+    Og, lseg = gd["O"].view, gd["lse"].view
     nv.attn_fwd(cu(c["Q"]), cu(kt), cu(c["V"]), Og, lseg, *meta, H, c["max_q"], c["causal"], c["scale"], max_k=c["max_k"], k_prescaled=True)
-    check(Og, O, 1.5e-2, "prescaled keys %s O" % (case,))
-    check(lseg, lse, 2e-3, "prescaled keys %s lse" % (case,))
-    got = [torch.full((Mq, d), float("nan"), dtype=BF16, device="cuda")] + \
-          [torch.full((Mk, d), float("nan"), dtype=BF16, device="cuda") for _ in range(2)]
+    check_attn(gd["O"], Og, O, c, "O", 1.5e-2, L_ATTN["O"], "prescaled keys %s O" % (case,))
+    check_attn(gd["lse"], lseg, lse, c, "lse", 2e-3, L_ATTN["lse"], "prescaled keys %s lse" % (case,))
+    got = [gd[n].view for n in ("dQ", "dK", "dV")]
     nv.attn_bwd(cu(c["Q"]), cu(kt), cu(c["V"]), None, cu(c["dO"]), cu(lse), cu(delta), *got, *meta, H, c["max_q"], c["max_k"], c["causal"],
                 c["scale"], k_prescaled=True)
-    for g_, r_, nm, tol, off, ln in zip(got, ref, ("dQ", "dK", "dV"), (2.5e-2, 2.5e-2, 2e-2), ("q_off", "k_off", "k_off"),
-                                        ("q_len", "k_len", "k_len")):
-        rows = torch.cat([torch.arange(int(o), int(o) + int(n)) for o, n in zip(c[off], c[ln])])
-        assert torch.isfinite(g_.float().cpu()[rows]).all(), "non-finite %s %s" % (nm, case)
-        check(g_.cpu()[rows], r_[rows], tol, "prescaled keys %s %s" % (case, nm))
+    for g_, r_, nm, tol in zip(got, ref, ("dQ", "dK", "dV"), (2.5e-2, 2.5e-2, 2e-2)):
+        check_attn(gd[nm], g_, r_, c, nm, tol, L_ATTN[nm], "prescaled keys %s %s" % (case, nm))
     # ... and the result is that of the plain call on the unscaled keys, up to the keys' one extra rounding realisation
     plain = [torch.zeros(Mq, d, dtype=BF16, device="cuda")] + [torch.zeros(Mk, d, dtype=BF16, device="cuda") for _ in range(2)]
     nv.attn_bwd(cu(c["Q"]), cu(c["K"]), cu(c["V"]), None, cu(c["dO"]), cu(lse), cu(delta), *plain, *meta, H, c["max_q"], c["max_k"],
@@ -496,7 +602,8 @@ def test_attention_prescaled_keys(case):
         check(g_.cpu()[rows], p_.cpu()[rows], 3e-2, "prescaled vs plain keys %s %s" % (case, nm))
     Lq, Lk = c["max_q"], c["max_k"]
     P = nv.attn_probs(cu(c["Q"]), cu(kt), *meta, H, Lq, Lk, c["causal"], c["scale"], k_prescaled=True)
-    check(P, em.attn_probs(c["Q"], kt, *meta_c, H, Lq, Lk, c["causal"], c["scale"], k_prescaled=True), 1e-4, "attn_probs, prescaled keys %s" % (case,))
+    check(P, em.attn_probs(c["Q"], kt, *meta_c, H, Lq, Lk, c["causal"], c["scale"], k_prescaled=True), 1e-4, "attn_probs, prescaled keys %s" % (case,),
+          tol_local=L_PROBS)
 
 
 def test_attention_backward_streams_stay_accurate_when_attention_is_sharp():
@@ -540,9 +647,13 @@ def test_attention_backward_streams_stay_accurate_when_attention_is_sharp():
         lse = torch.empty(H * M, dtype=F32, device="cuda")
         nv.attn_fwd(cu(Q), cu(Kx), cu(V), O, lse, *meta, H, max(lens), False, scale, max_k=max(lens), ores=Ores, k_prescaled=prescaled)
         delta = (cu(dO).float() * (O.float() + Ores.float())).view(M, H, dk).sum(-1).t().contiguous().view(-1)
-        got = [torch.full((M, d), float("nan"), dtype=BF16, device="cuda") for _ in range(3)]
+        gds = [GO(M, d) for _ in range(3)]
+        got = [gd.view for gd in gds]
         nv.attn_bwd(cu(Q), cu(Kx), cu(V), None, cu(dO), lse, delta, *got, *meta, H, max(lens), max(lens), False, scale, k_prescaled=prescaled)
         ref = reference(Kx, prescaled)
+        for gd, a, r, nm in zip(gds, got, ref, ("dQ", "dK", "dV")):
+            gd.assert_intact("sharp attention, streams=%s: %s" % (streams, nm))
+            check_local(a, r, L_ATTN[nm], "sharp attention, streams=%s: %s vs fp64" % (streams, nm))
         return [float((a.double().cpu() - r).norm() / r.norm()) for a, r in zip(got, ref)]
 
     try:
@@ -578,7 +689,7 @@ def test_attn_probs_kernel_vs_reference_maps(name, golden_dir):
     ref = torch.from_numpy(fx["f64/attn"])
     assert tuple(P.shape) == tuple(ref.shape)
     check(P, ref, 1.5e-2, "attn_probs %s" % name)
-    check(P, em.attn_probs(Q, K, q_off, q_len, k_off, k_len, H, Lq, Lk, causal, 1 / math.sqrt(d // H)), 1e-5, "attn_probs vs emulation %s" % name)
+    check(P, em.attn_probs(Q, K, q_off, q_len, k_off, k_len, H, Lq, Lk, causal, 1 / math.sqrt(d // H)), 1e-5, "attn_probs vs emulation %s" % name, tol_local=L_PROBS)
 
 
 def test_attention_work_lists_match_plain_enumeration():
@@ -649,39 +760,119 @@ def test_attention_long64_range_fallback():
 
 
 # ---- streaming kernels ----------------------------------------------------------------------
-def test_misc_kernels():
-    B, T, Fd, D, L, V = 3, 50, 80, 128, 12, 30
-    lens, tl = torch.tensor([50, 20, 33]), torch.tensor([12, 5, 9])
-    off = torch.tensor([0, 50, 70], dtype=I32)
-    toff = torch.tensor([0, 12, 17], dtype=I32)
+MISC_CASES = [
+    # B, T, Fd, D, L, V, lens, target lens
+    (3, 50, 80, 128, 12, 30, [50, 20, 33], [12, 5, 9]),
+    (3, 40, 80, 256, 12, 30, [1, 40, 17], [12, 1, 7]),          # an utterance of one frame, one that fills T, a token row with repeats
+    (2, 50, 80, 512, 65, 30, [50, 33], [65, 30]),               # d_model 512, more than 64 target positions
+]
+
+
+@pytest.mark.parametrize("B,T,Fd,D,L,V,lens,tl", MISC_CASES)
+def test_misc_kernels(B, T, Fd, D, L, V, lens, tl):
+    """The streaming kernels against their emulation, every output inside guards (NaN / a bit pattern, the window included:
+    what a kernel must write and did not stays visible).  unpack_rows writes zeros past an utterance's length (its contract),
+    so its whole output is compared; embed_bwd accumulates on top of ones, colliding atomics where a token repeats."""
+    lens, tl = torch.tensor(lens), torch.tensor(tl)
+    off = (torch.cumsum(lens, 0) - lens).to(I32)
+    toff = (torch.cumsum(tl, 0) - tl).to(I32)
     x = g(B, T, Fd, seed=1, dtype=F32)
-    rows = int(lens.sum())
+    rows, trows = int(lens.sum()), int(tl.sum())
+    tok = torch.randint(0, V, (B, L), generator=torch.Generator().manual_seed(3))
+    tok[0, 1:L:2] = tok[0, 0]                                    # repeats inside one row: embed_bwd's atomics collide
+    emb, pe = g(V, D, seed=4, dtype=F32), g(L, D, seed=5, dtype=F32)
+    xw = g(B, T, 1040, seed=2, dtype=F32)        # more float4 chunks per frame than threads in a workgroup
+    gds = {}
     for dev, mod in (("cpu", em), ("cuda", nv)):
         mv = lambda t: t.to(dev)
-        out = torch.zeros(rows, Fd, dtype=BF16, device=dev)
+        if dev == "cpu":
+            out, outw = torch.zeros(rows, Fd, dtype=BF16), torch.zeros(rows, 1040, dtype=BF16)
+            back = torch.full((B, T, Fd), 7.0, dtype=F32)
+            pg, pos = torch.zeros(rows, Fd, dtype=BF16), torch.zeros(rows, dtype=I32)
+            eo, demb, sh = torch.zeros(trows, D, dtype=BF16), torch.ones(V, D, dtype=F32), torch.zeros(V * D, dtype=BF16)
+        else:
+            gds = dict(pack=GO(rows, Fd, contiguous=True), pack_wide=GO(rows, 1040, contiguous=True),
+                       unpack=GO(B * T, Fd, F32, contiguous=True, shape=(B, T, Fd)), pack_grad=GO(rows, Fd), pos=GV(rows, I32),
+                       embed=GO(trows, D, contiguous=True), demb=GO(V, D, F32, contiguous=True), cast=GV(V * D, BF16))
+            gds["demb"].view.fill_(1.0)
+            out, outw, back, pg, pos, eo, demb, sh = (gds[k].view for k in ("pack", "pack_wide", "unpack", "pack_grad", "pos", "embed",
+                                                                            "demb", "cast"))
         mod.pack_rows(mv(x), mv(off), mv(lens.to(I32)), out)
-        back = torch.full((B, T, Fd), 7.0, dtype=F32, device=dev)
         mod.unpack_rows(out, mv(off), mv(lens.to(I32)), back)
-        pg = torch.zeros(rows, Fd, dtype=BF16, device=dev)
         mod.pack_grad(mv(x), mv(off), mv(lens.to(I32)), pg)
-        pos = torch.zeros(rows, dtype=I32, device=dev)
-        mod.row_index(mv(off), mv(lens.to(I32)), 50, pos)
-        tok = torch.randint(0, V, (B, L), generator=torch.Generator().manual_seed(3))
-        emb, pe = g(V, D, seed=4, dtype=F32), g(L, D, seed=5, dtype=F32)
-        eo = torch.zeros(int(tl.sum()), D, dtype=BF16, device=dev)
+        mod.row_index(mv(off), mv(lens.to(I32)), T, pos)
         mod.embed_pe_fwd(mv(tok), mv(emb), mv(pe), mv(toff), mv(tl.to(I32)), eo)
-        demb = torch.ones(V, D, dtype=F32, device=dev)
         mod.embed_bwd(mv(tok), eo, mv(toff), mv(tl.to(I32)), 0, demb)
-        xw = g(B, T, 1040, seed=2, dtype=F32)        # more float4 chunks per frame than threads in a workgroup
-        outw = torch.zeros(rows, 1040, dtype=BF16, device=dev)
         mod.pack_rows(mv(xw), mv(off), mv(lens.to(I32)), outw)
-        sh = torch.zeros(V * D, dtype=BF16, device=dev)
         mod.cast_bf16(mv(emb).view(-1), sh)
         res = dict(pack=out, pack_wide=outw, unpack=back, pack_grad=pg, pos=pos, embed=eo, demb=demb, cast=sh)
         if dev == "cpu":
             ref = res
     for k in ref:
-        check(res[k], ref[k], 3e-3 if k == "demb" else 1e-6, "misc %s" % k)
+        tol = 3e-3 if k == "demb" else 1e-6
+        check(res[k], ref[k], tol, "misc %s" % k, tol_local=L_BF16 if res[k].dtype == BF16 else tol)
+        gds[k].assert_intact("misc %s" % k)
+    for b in range(B):          # zeros past every length, written by the kernel (the window started as NaN)
+        assert float(res["unpack"][b, int(lens[b]):].abs().sum()) == 0
+
+
+@pytest.mark.parametrize("D", [128, 256, 512])
+@pytest.mark.parametrize("n", [1, 37, 320])
+def test_embed_step_equals_the_emulation(n, D):
+    """st_embed_step: out = bf16(emb[token] + pe[*step]) - one rounding, bit for bit the emulation's; at the first and the last
+    row of the positional table."""
+    V, pe_rows = 53, 21
+    gen = torch.Generator().manual_seed(n + D)
+    tokens = torch.randint(0, V, (n,), generator=gen)
+    tokens[0], tokens[-1] = V - 1, 0
+    emb, pe = g(V, D, seed=1, dtype=F32), g(pe_rows, D, seed=2, dtype=F32)
+    for t in (0, pe_rows - 1):
+        step = torch.tensor([t], dtype=torch.long)
+        gd = GO(n, D, contiguous=True)
+        nv.embed_step(cu(tokens), cu(emb), cu(pe), cu(step), gd.view)
+        ref = em.embed_step(tokens, emb, pe, step, torch.zeros(n, D, dtype=BF16))
+        assert torch.equal(gd.view.cpu(), ref), "embed_step n=%d D=%d step %d" % (n, D, t)
+        gd.assert_intact("embed_step n=%d D=%d step %d" % (n, D, t))
+
+
+@pytest.mark.parametrize("L,n,S,W,beam", [(2, 20, 9, 512, 10), (1, 32, 5, 1024, 16),       # beam * W / 8 = 2,048: the wrapper's limit
+                                          (3, 6, 4, 256, 1)])
+@pytest.mark.parametrize("order_kind", ["rotation", "one-slot", "identity"])
+def test_cache_reorder_equals_the_emulation(L, n, S, W, beam, order_kind):
+    """st_cache_reorder gathers an utterance's rows IN PLACE: a rotation (every row is read after another was due to be written), one
+    slot copied to every row of its utterance, the identity - bit for bit the emulation's gather on a copy; positions past *step
+    keep their bits, nothing around the cache is written."""
+    slots = torch.arange(beam)
+    within = {"rotation": (slots + 1) % beam, "one-slot": torch.full((beam,), beam - 1), "identity": slots}[order_kind]
+    order = (torch.arange(n // beam).view(-1, 1) * beam + within.view(1, -1)).reshape(-1)
+    cache = g(L, n, S, W, seed=L + n)
+    step = torch.tensor([S - 3], dtype=torch.long)               # below S - 1: two positions must stay as they are
+    gd = GO(L * n * S, W, contiguous=True, shape=(L, n, S, W))
+    gd.view.copy_(cache)
+    nv.cache_reorder(gd.view, cu(order), cu(step), beam)
+    ref = em.cache_reorder(cache.clone(), order, step, beam)
+    got = gd.view.cpu()
+    assert torch.equal(got[:, :, S - 2:], cache[:, :, S - 2:]), "positions past *step changed"
+    assert torch.equal(got, ref), "cache_reorder %s differs from the gather" % order_kind
+    gd.assert_intact("cache_reorder %s" % order_kind)
+
+
+@pytest.mark.parametrize("R,V,ld", [(1, 2, 8), (7, 30, 40), (1206, 4337, 4344), (5, 5121, 5128)])
+def test_ctc_best_path_is_the_row_argmax(R, V, ld):
+    """st_ctc_best_path == argmax over the first V columns: the padding columns hold a value above every real logit (reading past V
+    would win), one row ties exactly at its first and last valid column (the lower id wins)."""
+    gen = torch.Generator().manual_seed(V)
+    logits = torch.full((R, ld), 1e30)
+    logits[:, :V] = torch.randn(R, V, generator=gen) * 3
+    tie = R // 2
+    logits[tie, 0] = logits[tie, V - 1] = 50.0
+    want = torch.argmax(logits[:, :V], dim=1).to(I32)
+    want[tie] = 0
+    gd = GV(R, I32)
+    nv.ctc_best_path(GI(logits, pad_cols=(0, 0)), V, gd.view)          # (row guards only: the leading dimension is the case's)
+    got = gd.view.cpu()
+    assert torch.equal(got, want), "ctc_best_path: rows %s differ" % torch.nonzero(got != want).flatten()[:10].tolist()
+    gd.assert_intact("ctc_best_path")
 
 
 # ---- training-mode dropout: counter-based masks, bit-identical to the emulation's hash -----------------
@@ -775,21 +966,28 @@ def test_attention_dropout(case):
         meta = [mv(c[k]) for k in ("q_off", "q_len", "k_off", "k_len")]
         O = torch.zeros(c["Mq"], c["d"], dtype=BF16, device=dev)
         lse = torch.zeros(c["H"] * c["Mq"], dtype=F32, device=dev)
-        fwd(Q, K, V, O, lse, *meta, c["H"], c["max_q"], c["causal"], c["scale"], drop=d, max_k=c["max_k"])
-        delta = torch.zeros_like(lse)
         dQ = torch.zeros(c["Mq"], c["d"], dtype=BF16, device=dev)
         dK, dV = (torch.zeros(c["Mk"], c["d"], dtype=BF16, device=dev) for _ in range(2))
+        delta = torch.zeros_like(lse)
+        if dev == "cuda" and d is not None:
+            gd.update(_attn_guards(c))
+            O, lse, dQ, dK, dV, delta = (gd[n].view for n in ("O", "lse", "dQ", "dK", "dV", "delta"))
+        fwd(Q, K, V, O, lse, *meta, c["H"], c["max_q"], c["causal"], c["scale"], drop=d, max_k=c["max_k"])
         bwd(Q, K, V, O, dO, lse, delta, dQ, dK, dV, *meta, c["H"], c["max_q"], c["max_k"], c["causal"], c["scale"],
             drop=d)
-        return O, lse, dQ, dK, dV
+        return O, lse, dQ, dK, dV, delta
 
+    gd = {}
     r = run(em.attn_fwd, em.attn_bwd, "cpu", de)
     o = run(nv.attn_fwd, nv.attn_bwd, "cuda", dn)
     for got, ref, nm, tol in zip(o, r, ("O", "lse", "dQ", "dK", "dV"), (2e-2, 2e-3, 3e-2, 3e-2, 2.5e-2)):
-        check(got, ref, tol, "attention dropout %s %s" % (case, nm))
+        check_attn(gd[nm], got, ref, c, nm, tol, L_ATTN_DROP[nm], "attention dropout %s %s" % (case, nm))
+    check_attn(gd["delta"], o[5], _delta_of(c["dO"], o[0], c["H"]), c, "delta", 2e-3, L_ATTN_DROP["delta"], "attention dropout %s delta" % (case,))
+    check_attn(None, o[5], r[5], c, "delta", 2e-2, None, "attention dropout %s delta vs the emulation's" % (case,))
     # and the masks really are drawn: the dropout-free output differs
     o0 = run(nv.attn_fwd, nv.attn_bwd, "cuda", None)
-    assert rel(o[0], o0[0]) > 5e-2
+    rows = _attn_rows(c, "O")
+    assert rel(o[0].cpu()[rows], o0[0].cpu()[rows]) > 5e-2
 
 
 def test_wgrad_group_matches_individual_launches():
@@ -797,20 +995,27 @@ def test_wgrad_group_matches_individual_launches():
     gradient, more than one launch's worth) in one call == the same problems launched one by one."""
     shapes = [(1206, 768, 256, 4, True), (1206, 256, 256, 2, True), (1206, 1024, 256, 4, True),
               (1206, 256, 1024, 1, False), (333, 128, 80, 3, True), (50, 4344, 256, 1, False)] * 9      # 54 > GROUP_MAX
-    probs, ref = [], []
+    probs, ref, gds = [], [], []
     for q, (m, n, k, sp, with_b) in enumerate(shapes):
         dy, x = cu(g(m, n, seed=10 + q)), cu(g(m, k, seed=60 + q))
         init, b0 = g(n, k, seed=5, dtype=F32), g(1, n, seed=6, dtype=F32).view(-1)
-        gw, gb = cu(init.clone()), (cu(b0.clone()) if with_b else None)
+        gdw, gdb = GO(n, k, F32), (GV(n) if with_b else None)
+        gdw.view.copy_(init)
+        if with_b:
+            gdb.view.copy_(b0)
+        gds.append((gdw, gdb))
+        gw, gb = gdw.view, (gdb.view if with_b else None)
         probs.append((x, dy, gw, gb, sp, n))
         rw, rb = cu(init.clone()), (cu(b0.clone()) if with_b else None)
         nv.gemm(x, dy, rw, bias=rb, epi=nv.EPI_F32_ATOMIC_T, x_cmajor=True, y_cmajor=True, splits=sp, n=n)
         ref.append((rw, rb))
     nv.wgrad_group(probs)
     for q, ((_, _, gw, gb, _, _), (rw, rb)) in enumerate(zip(probs, ref)):
-        check(gw, rw, 1e-5, "wgrad_group dW problem %d" % q)       # same kernel body; only the atomic order differs
+        check(gw, rw, 1e-5, "wgrad_group dW problem %d" % q, tol_local=L_F32)       # same kernel body; only the atomic order differs
+        gds[q][0].assert_intact("wgrad_group dW problem %d" % q)
         if gb is not None:
-            check(gb, rb, 1e-5, "wgrad_group db problem %d" % q)
+            check(gb, rb, 1e-5, "wgrad_group db problem %d" % q, tol_local=L_F32)
+            gds[q][1].assert_intact("wgrad_group db problem %d" % q)
 
 
 def test_wgrad_wide_matches_fp32():
@@ -821,17 +1026,24 @@ def test_wgrad_wide_matches_fp32():
     shapes = [(9000, 768, 256, 3, True), (8200, 256, 256, 7, True), (8300, 1024, 256, 2, True),
               (8192, 256, 1024, 1, False), (333, 296, 200, 3, True), (50, 520, 256, 5, False),
               (1000, 264, 72, 4, True)] * 7      # 49 > WIDE_MAX
-    probs, ref = [], []
+    probs, ref, gds = [], [], []
     for q, (m, n, k, sp, with_b) in enumerate(shapes):
         dy, x = g(m, n, seed=10 + q), g(m, k, seed=60 + q)
         init, b0 = g(n, k, seed=5, dtype=F32), g(1, n, seed=6, dtype=F32).view(-1)
-        probs.append((cu(x), cu(dy), cu(init.clone()), cu(b0.clone()) if with_b else None, sp, n))
+        gdw, gdb = GO(n, k, F32), (GV(n) if with_b else None)
+        gdw.view.copy_(init)
+        if with_b:
+            gdb.view.copy_(b0)
+        gds.append((gdw, gdb))
+        probs.append((cu(x), cu(dy), gdw.view, gdb.view if with_b else None, sp, n))
         ref.append((init + dy.float().t() @ x.float(), b0 + dy.float().sum(0)))
     nv.wgrad_group(probs, wide=True)
     for q, ((_, _, gw, gb, _, _), (rw, rb)) in enumerate(zip(probs, ref)):
-        check(gw, rw, 2e-5, "wgrad_wide dW problem %d" % q)
+        check(gw, rw, 2e-5, "wgrad_wide dW problem %d" % q, tol_local=L_F32)
+        gds[q][0].assert_intact("wgrad_wide dW problem %d" % q)
         if gb is not None:
-            check(gb, rb, 2e-5, "wgrad_wide db problem %d" % q)
+            check(gb, rb, 2e-5, "wgrad_wide db problem %d" % q, tol_local=L_F32)
+            gds[q][1].assert_intact("wgrad_wide db problem %d" % q)
 
 
 def test_wgrad_wide_at_decoder_side_shapes_through_the_plan():
@@ -858,8 +1070,19 @@ def test_wgrad_wide_at_decoder_side_shapes_through_the_plan():
 
 def test_feat_stack_kernel():
     """st_feat_stack (CMVN + frame stacking + subsampling + ragged pack) against the oracle restatement of Dataset.py."""
+    from st_amd.features import stack_frames
     from tests import test_features_cpu as tf
     tf.run_stack_frames("cuda")
+    # the same launches into a guarded buffer (its window zeroed, as stack_frames hands it over): the same bits, nothing written around
+    for left, right, rate in ((3, 0, 10), (2, 1, 20)):
+        x, lens, stats = tf._case(left, right, rate, True, 10)
+        ref, rows = stack_frames(x.cuda(), lens, left, right, rate, stats.cuda())
+        gd = GO(rows.total, ref.shape[1])
+        gd.view.zero_()
+        nv.feat_stack(x.cuda(), lens.to("cuda", I32), stats.cuda(), left, right, 1 if rate == 10 else rate // 10, rows.off, rows.len,
+                      rows.max_len, gd.view)
+        assert torch.equal(gd.view, ref), "feat_stack into a strided view differs (%d, %d, %d)" % (left, right, rate)
+        gd.assert_intact("feat_stack (%d, %d, %d)" % (left, right, rate))
 
 
 @pytest.mark.parametrize("M,N,K,hd", [(333, 256, 256, 64), (1000, 128, 128, 32), (130, 512, 512, 64), (260, 512, 512, 128)])
@@ -870,13 +1093,14 @@ def test_gemm_dgrad_with_delta_epilogue(M, N, K, hd):
     ref_d = torch.zeros(H * M, dtype=F32)
     ref = em.gemm(dy, W, torch.zeros(M, N, dtype=BF16), aux=O, epi=nv.EPI_BF16_DELTA, y_cmajor=True, delta=ref_d,
                   head_dim=hd)
-    got_d = torch.full((H * M,), float("nan"), dtype=F32, device="cuda")
-    got = nv.gemm(cu(dy), cu(W), torch.zeros(M, N, dtype=BF16, device="cuda"), aux=cu(O), epi=nv.EPI_BF16_DELTA,
-                  y_cmajor=True, delta=got_d, head_dim=hd)
-    check(got, ref, 1e-2, "dgrad+delta out")
+    gdd, gdo = GV(H * M), GO(M, N)
+    got_d = gdd.view
+    got = nv.gemm(GI(dy), GI(W), gdo.view, aux=GI(O), epi=nv.EPI_BF16_DELTA, y_cmajor=True, delta=got_d, head_dim=hd)
+    check(got, ref, 1e-2, "dgrad+delta out", tol_local=L_BF16)
     # delta is a sum of products of bf16 values: compare against the kernel's OWN bf16 output to isolate the reduction
     own = (got.float().cpu() * O.float()).view(M, H, hd).sum(-1).t().reshape(-1)
-    check(got_d, own, 1e-5, "dgrad+delta delta")
+    check(got_d, own, 1e-5, "dgrad+delta delta", tol_local=L_F32)
+    gdd.assert_intact("dgrad+delta delta"), gdo.assert_intact("dgrad+delta out")
 
 
 @pytest.mark.parametrize("case", [(3, 4, 64, None, [200, 131, 64], False, True), (2, 4, 64, [50, 33], [1000, 517], False, True),
@@ -900,17 +1124,24 @@ def test_attention_backward_single_launch(case):
         dK, dV = (torch.zeros(c["Mk"], c["d"], dtype=BF16, device="cuda") for _ in range(2))
         if single:
             delta = outs[0][3].clone()
+            gd = _attn_guards(c)
+            dQ, dK, dV = (gd[n].view for n in ("dQ", "dK", "dV"))
+        else:                  # the two-kernel pass computes delta itself: inside guards, against rowsum(dO * O) of the O it read
+            gdd = GV(c["H"] * c["Mq"])
+            delta = gdd.view
         nv.attn_bwd(Q, K, V, None if single else O, dO, lse, delta, dQ, dK, dV, *meta, c["H"], c["max_q"], c["max_k"],
                     c["causal"], c["scale"])
         outs.append((dQ, dK, dV, delta))
+    check_attn(gdd, outs[0][3], _delta_of(dO, O, c["H"]), c, "delta", 1e-5, L_ATTN["delta"], "two-kernel backward: delta")
     streams = case[2] == 64 and not case[5] and min(c["max_q"], c["max_k"]) > 128
     # (few queries against many keys: the one-launch form cuts the dQ items' keys over workgroups - other fp32 partial sums, round 6)
     split = nv.load()._cdll.st_attn_bwd_split_kib(case[0], c["H"], case[2], c["max_q"], c["max_k"], int(case[5])) > 0
     for a, b, nm in zip(outs[0][:3], outs[1][:3], ("dQ", "dK", "dV")):
+        gd[nm].assert_intact("single-launch backward %s" % nm)
         if streams:
-            check(b, a, 6e-3, "single-launch backward (hand-scheduled streams) %s" % nm)
+            check(b, a, 6e-3, "single-launch backward (hand-scheduled streams) %s" % nm, tol_local=L_ATTN[nm])
         elif split and nm == "dQ":
-            check(b, a, 6e-3, "single-launch backward (keys split across workgroups) %s" % nm)
+            check(b, a, 6e-3, "single-launch backward (keys split across workgroups) %s" % nm, tol_local=L_ATTN[nm])
         else:
             assert torch.equal(a, b), "single-launch backward changed %s" % nm
 
@@ -944,14 +1175,17 @@ def test_attention_backward_streams_with_dropout(lens, p, monkeypatch):
     for mode in ("e", "1"):
         monkeypatch.setenv("ST_ATTN_BWD64", mode)
         nv.env_refresh()          # (the library caches its development switches)
-        got = [torch.full((M, d), float("nan"), dtype=BF16, device="cuda") for _ in range(3)]
+        gds = [GO(M, d) for _ in range(3)]
+        got = [gd.view for gd in gds]
         nv.attn_bwd(Q, K, V, None, dO, lse, delta, *got, q_off, q_len, q_off, q_len, H, max(lens), max(lens), False, scale,
                     work_q=wq, work_k=wk, drop=drop)
         torch.cuda.synchronize()
+        for gd, nm in zip(gds, ("dQ", "dK", "dV")):
+            gd.assert_intact("backward streams with dropout p = %s, ST_ATTN_BWD64=%s: %s" % (p, mode, nm))
         outs[mode] = got
     for a, b, nm in zip(outs["e"], outs["1"], ("dQ", "dK", "dV")):
         assert torch.isfinite(b.float()).all(), nm
-        check(b, a, 6e-3, "backward streams with dropout p = %s: %s" % (p, nm))
+        check(b, a, 6e-3, "backward streams with dropout p = %s: %s" % (p, nm), tol_local=L_ATTN_DROP[nm])
     # and the masks matter: without them the result is far away (guards against a variant that silently ignores the Drop)
     monkeypatch.delenv("ST_ATTN_BWD64")
     nv.env_refresh()
@@ -975,14 +1209,23 @@ def test_gemm_lnbwd(M, N, K, with_aux, p):
 
     def run(fn, dev, d):
         mv = (lambda t: None if t is None else t.to(dev))
-        dx = torch.zeros(M, N, dtype=BF16, device=dev)
-        acc = [torch.ones(N, dtype=F32, device=dev) for _ in range(3)]
-        fn(mv(dY), mv(W), mv(aux), mv(xhat), mv(rstd), mv(gamma), dx, acc[0], acc[1], acc[2], drop=d)
+        op = mv
+        if dev == "cuda":
+            gds.extend([GO(M, N)] + [GV(N) for _ in range(3)])
+            for gd in gds[1:]:
+                gd.view.fill_(1.0)
+            dx, acc, op = gds[0].view, [gd.view for gd in gds[1:]], GI
+        else:
+            dx, acc = torch.zeros(M, N, dtype=BF16), [torch.ones(N, dtype=F32) for _ in range(3)]
+        fn(op(dY), mv(W), op(aux), mv(xhat), mv(rstd), mv(gamma), dx, acc[0], acc[1], acc[2], drop=d)
         return [dx] + acc
 
-    r, o = run(em.gemm_lnbwd, "cpu", de), run(nv.gemm_lnbwd, "cuda", dn)
-    for got, ref, nm, tol in zip(o, r, ("dx", "dgamma", "dbeta", "dbias"), (1.5e-2, 5e-3, 5e-3, 8e-3)):
-        check(got, ref, tol, "gemm_lnbwd %s %s" % ((M, N, K, with_aux, p), nm))
+    gds = []
+    # (the kernel sums dx as stored for dbias: the emulation is asked for that rounding point)
+    r, o = run(functools.partial(em.gemm_lnbwd, dbias_rounded=True), "cpu", de), run(nv.gemm_lnbwd, "cuda", dn)
+    for got, ref, nm, tol, gd in zip(o, r, ("dx", "dgamma", "dbeta", "dbias"), (1.5e-2, 5e-3, 5e-3, 8e-3), gds):
+        check(got, ref, tol, "gemm_lnbwd %s %s" % ((M, N, K, with_aux, p), nm), tol_local=L_GEMM_LNBWD[nm])
+        gd.assert_intact("gemm_lnbwd %s %s" % ((M, N, K, with_aux, p), nm))
 
 
 @pytest.mark.parametrize("M,blocks,rows,K", [(700, 3, 256, 128), (1206, 6, 512, 256), (77, 2, 128, 80)])
@@ -1002,8 +1245,10 @@ def test_gemm_stacked_weights(M, blocks, rows, K):
     Kp = ldy
     xp = torch.zeros(M, Kp, dtype=BF16, device="cuda")
     xp[:, :K] = x
-    out, ref = torch.empty(M, blocks * rows, dtype=BF16, device="cuda"), torch.empty(M, blocks * rows, dtype=BF16, device="cuda")
-    nv.gemm(xp[:, :K], W0, out, bias=b0, stack=(blocks, w_stride, b_stride))
+    gd, ref = GO(M, blocks * rows), torch.empty(M, blocks * rows, dtype=BF16, device="cuda")
+    out = nv.gemm(xp[:, :K], W0, gd.view, bias=b0, stack=(blocks, w_stride, b_stride))
+    gd.assert_intact("stacked forward")
+    assert torch.isfinite(out.float()).all()
     wc = torch.zeros(blocks * rows, Kp, dtype=BF16, device="cuda")
     wc[:, :K] = Wcat
     nv.gemm(xp[:, :K], wc[:, :K], ref, bias=bcat)
@@ -1011,8 +1256,10 @@ def test_gemm_stacked_weights(M, blocks, rows, K):
     # dgrad: dx[M, K] = dy[M, blocks * rows] @ stack (+ aux)
     if K % 8 == 0:
         dy, aux = cu(g(M, blocks * rows, seed=4)), cu(g(M, K, seed=5))
-        dx, dref = torch.empty(M, K, dtype=BF16, device="cuda"), torch.empty(M, K, dtype=BF16, device="cuda")
-        nv.gemm(dy, W0, dx, y_cmajor=True, stack=(blocks, w_stride, 0), epi=nv.EPI_BF16_ADD, aux=aux)
+        gdx, dref = GO(M, K), torch.empty(M, K, dtype=BF16, device="cuda")
+        dx = nv.gemm(dy, W0, gdx.view, y_cmajor=True, stack=(blocks, w_stride, 0), epi=nv.EPI_BF16_ADD, aux=aux)
+        gdx.assert_intact("stacked dgrad")
+        assert torch.isfinite(dx.float()).all()
         nv.gemm(dy, Wcat, dref, y_cmajor=True, epi=nv.EPI_BF16_ADD, aux=aux)
         assert torch.equal(dx, dref), "stacked dgrad differs from the gathered GEMM"
 
@@ -1023,11 +1270,13 @@ def test_gemm_kscale_scales_the_key_block_before_its_rounding(M, d, K):
     per-GEMM path's form of st_row_chain's post_kscale); the other two blocks are st_gemm's, bit for bit."""
     x, W, b = g(M, K, seed=1), g(3 * d, K, seed=2, scale=K ** -0.5), g(3 * d, seed=3, dtype=F32)
     ks = 0.125 * nv.K_LOG2_SCALE
-    got = nv.gemm_kscale(cu(x), cu(W), torch.full((M, 3 * d), float("nan"), dtype=BF16, device="cuda"), cu(b), d, 2 * d, ks)
+    gd = GO(M, 3 * d)
+    got = nv.gemm_kscale(GI(x), cu(W), gd.view, cu(b), d, 2 * d, ks)
+    gd.assert_intact("gemm_kscale")
     plain = nv.gemm(cu(x), cu(W), torch.zeros(M, 3 * d, dtype=BF16, device="cuda"), bias=cu(b))
     assert torch.equal(got[:, :d], plain[:, :d]) and torch.equal(got[:, 2 * d:], plain[:, 2 * d:])
     ref = em.gemm_kscale(x, W, torch.zeros(M, 3 * d, dtype=BF16), b, d, 2 * d, ks)
-    check(got, ref, 1e-2, "gemm_kscale")
+    check(got, ref, 1e-2, "gemm_kscale", tol_local=L_BF16)
     acc = (x.float() @ W.float().t() + b)[:, d:2 * d] * ks
     err_once = (got[:, d:2 * d].float().cpu() - acc).norm() / acc.norm()
     err_twice = ((plain[:, d:2 * d].float().cpu() * ks).to(BF16).float() - acc).norm() / acc.norm()
@@ -1139,15 +1388,15 @@ def test_gemm_ws_forward(M, N, relu):
     K = 256
     x, W, b = g(M, K, seed=1), g(N, K, seed=2, scale=K ** -0.5), g(N, seed=3, dtype=F32)
     ref = em.gemm(x, W, torch.zeros(M, N, dtype=BF16), bias=b, epi=nv.EPI_BF16_RELU if relu else nv.EPI_BF16)
-    xw = torch.zeros(M, K + 64, dtype=BF16, device="cuda")
-    xw[:, 8:8 + K] = cu(x)
-    ow = torch.full((M + 3, N + 128), float("nan"), dtype=BF16, device="cuda")
-    out = nv.gemm_ws(xw[:, 8:8 + K], cu(W), ow[:M, 64:64 + N], bias=cu(b), relu=relu)
-    check(out, ref, 1e-2, "gemm_ws %dx%d relu=%d" % (M, N, relu))
-    assert torch.isnan(ow[M:].float()).all() and torch.isnan(ow[:, :64].float()).all() and torch.isnan(ow[:, 64 + N:].float()).all(), \
-        "gemm_ws wrote outside its output view"
-    nb = nv.gemm_ws(cu(x), cu(W), torch.empty(M, N, dtype=BF16, device="cuda"), relu=relu)       # no bias
-    check(nb, em.gemm(x, W, torch.zeros(M, N, dtype=BF16), epi=nv.EPI_BF16_RELU if relu else nv.EPI_BF16), 1e-2, "gemm_ws no bias")
+    gd = GO(M, N)
+    out = nv.gemm_ws(GI(x, pad_cols=(8, 56)), cu(W), gd.view, bias=cu(b), relu=relu)
+    check(out, ref, 1e-2, "gemm_ws %dx%d relu=%d" % (M, N, relu), tol_local=L_BF16)
+    gd.assert_intact("gemm_ws %dx%d relu=%d" % (M, N, relu))
+    gd = GO(M, N, contiguous=True)
+    nb = nv.gemm_ws(cu(x), cu(W), gd.view, relu=relu)       # no bias
+    check(nb, em.gemm(x, W, torch.zeros(M, N, dtype=BF16), epi=nv.EPI_BF16_RELU if relu else nv.EPI_BF16), 1e-2, "gemm_ws no bias",
+          tol_local=L_BF16)
+    gd.assert_intact("gemm_ws no bias")
 
 
 @pytest.mark.parametrize("p", [0.1, 0.5])
@@ -1157,8 +1406,10 @@ def test_gemm_ws_relu_dropout_mask(p):
     x, W, b = g(M, K, seed=1), g(N, K, seed=2, scale=K ** -0.5), g(N, seed=3, dtype=F32)
     dn, de = _drops(11, p)
     ref = em.gemm(x, W, torch.zeros(M, N, dtype=BF16), bias=b, epi=nv.EPI_BF16_RELU, drop=de)
-    out = nv.gemm_ws(cu(x), cu(W), torch.zeros(M, N, dtype=BF16, device="cuda"), bias=cu(b), relu=True, drop=dn)
-    check(out, ref, 1e-2, "gemm_ws relu+dropout p=%g" % p)
+    gd = GO(M, N)
+    out = nv.gemm_ws(cu(x), cu(W), gd.view, bias=cu(b), relu=True, drop=dn)
+    check(out, ref, 1e-2, "gemm_ws relu+dropout p=%g" % p, tol_local=L_BF16)
+    gd.assert_intact("gemm_ws relu+dropout p=%g" % p)
     _zero_pattern_equal(out, ref, "gemm_ws relu+dropout p=%g" % p)
     tiled = nv.gemm(cu(x), cu(W), torch.zeros(M, N, dtype=BF16, device="cuda"), bias=cu(b), epi=nv.EPI_BF16_RELU, drop=dn)
     _zero_pattern_equal(out, tiled, "gemm_ws vs st_gemm dropout mask")
@@ -1248,11 +1499,13 @@ def test_gemm_ws_stacked_weights():
     Wcat = torch.cat([torch.as_strided(arena_w, (rows, K), (K, 1), 64 + l * w_stride) for l in range(blocks)]).contiguous()
     bcat = torch.cat([arena_b[32 + l * b_stride:32 + l * b_stride + rows] for l in range(blocks)]).contiguous()
     x = cu(g(M, K, seed=3))
-    out = nv.gemm_ws(x, W0, torch.empty(M, blocks * rows, dtype=BF16, device="cuda"), bias=b0, stack=(blocks, w_stride, b_stride))
+    gd = GO(M, blocks * rows)
+    out = nv.gemm_ws(x, W0, gd.view, bias=b0, stack=(blocks, w_stride, b_stride))
+    gd.assert_intact("stacked gemm_ws")
     ref = nv.gemm_ws(x, Wcat, torch.empty(M, blocks * rows, dtype=BF16, device="cuda"), bias=bcat)
     assert torch.equal(out, ref), "stacked gemm_ws differs from the gathered one"
     tiled = nv.gemm(x, W0, torch.empty(M, blocks * rows, dtype=BF16, device="cuda"), bias=b0, stack=(blocks, w_stride, b_stride))
-    check(out, tiled, 5e-3, "gemm_ws vs st_gemm_stacked")
+    check(out, tiled, 5e-3, "gemm_ws vs st_gemm_stacked", tol_local=L_BF16)
 
 
 @pytest.mark.parametrize("M,N,K,splits,ycm", [(1206, 256, 4344, 8, True), (5, 256, 2104, 3, True), (300, 384, 4096, 5, False),
@@ -1266,16 +1519,33 @@ def test_gemm_splitk_matches_gemm(M, N, K, splits, ycm):
     w = g(K, N, seed=2, scale=K ** -0.5) if ycm else g(N, K, seed=2, scale=K ** -0.5)
     ref = em.gemm(x, w, torch.zeros(M, N, dtype=BF16), y_cmajor=ycm)
     plain = nv.gemm(cu(x), cu(w), torch.zeros(M, N, dtype=BF16, device="cuda"), y_cmajor=ycm)
-    a = nv.gemm_splitk(cu(x), cu(w), torch.full((M, N), float("nan"), dtype=BF16, device="cuda"), splits, y_cmajor=ycm)
+    gd = GO(M, N)
+    a = nv.gemm_splitk(GI(x), GI(w), gd.view, splits, y_cmajor=ycm)
     b = nv.gemm_splitk(cu(x), cu(w), torch.full((M, N), float("nan"), dtype=BF16, device="cuda"), splits, y_cmajor=ycm)
-    check(a, ref, 1e-2, "gemm_splitk vs fp32 reference")
-    check(a, plain, 1e-2, "gemm_splitk vs st_gemm")
+    check(a, ref, 1e-2, "gemm_splitk vs fp32 reference", tol_local=L_BF16)
+    check(a, plain, 1e-2, "gemm_splitk vs st_gemm", tol_local=L_BF16)
+    gd.assert_intact("gemm_splitk")
     assert torch.equal(a, b), "gemm_splitk not reproducible"
     for wk in nv._splitk_work.values():
         assert int(wk[:1024].abs().sum()) == 0, "split-K tickets not reset"
 
 
 # ---- row chains (csrc/st_rowchain.hip) -----------------------------------------------------------------------------
+def _chain_fwd_guards(M, d, dff, p_cols):
+    """Every output of a forward chain inside guards: the wrapper fixes the leading dimension of all but P (row guards there)."""
+    return dict(out0=GO(M, d, contiguous=True), xhat0=GO(M, d, contiguous=True), rstd0=GV(M), H=GO(M, dff, contiguous=True),
+                out1=GO(M, d, contiguous=True), xhat1=GO(M, d, contiguous=True), rstd1=GV(M), P=GO(M, p_cols))
+
+
+def _chain_bwd_guards(M, d, dff, heads):
+    """... and of a backward chain; the column-sum accumulators keep their non-zero initial values."""
+    gd = dict(ds_a=GO(M, d, contiguous=True), dga=GV(d), dba=GV(d), dbia=GV(d), dH=GO(M, dff, contiguous=True), ds_b=GO(M, d, contiguous=True),
+              dgb=GV(d), dbb=GV(d), dbib=GV(d), dctx=GO(M, d), delta=GV(heads * M))
+    for n, v in (("dga", 1), ("dba", 2), ("dbia", 3), ("dgb", -1), ("dbb", -2), ("dbib", -3)):
+        gd[n].view.fill_(float(v))
+    return gd
+
+
 @pytest.mark.parametrize("M", [5, 320, 1206, 3120, 9000, 17000, 24700])      # 3120: 98 row blocks - a split chain takes two chunks per part; 24700: past one round of 96-row tiles -> two rounds of 64-row ones
 @pytest.mark.parametrize("variant", ["pre+post1", "pre+ffn+post3", "pre+ffn", "ffn", "ffn+post1", "pre+ffn+post3+drop",
                                      "pre+ffn+post3+split", "pre+ffn+split", "ffn+split", "ffn+post1+split", "pre+ffn+post3+drop+split",
@@ -1317,17 +1587,16 @@ def test_row_chain_matches_the_separate_kernels(M, variant):
         o = dict(out0=E(M, d), xhat0=E(M, d), rstd0=E(M, dt=F32), H=E(M, dff), out1=E(M, d), xhat1=E(M, d), rstd1=E(M, dt=F32),
                  P=E(M, 256 * max(nb, 1)))
         if dev == "cuda":
+            gd = _chain_fwd_guards(M, d, dff, 256 * max(nb, 1))
+            guards.append(gd)
+            o = {k: v.view for k, v in gd.items()}
             cs = chains.ChainSet("cuda")
             cid = cs.add(blocks("cuda"))
             cs.finalize().rebuild()
             ch = cs.chain(cid)
             if "split" in parts:        # the feed-forward's hidden dimension over 4 workgroups per row block (M <= 2048; else ignored)
                 ch.split_work = split_work
-            Aw = torch.zeros(M, d + 64, dtype=BF16, device="cuda")      # strided operand views
-            Aw[:, 32:32 + d] = f(A)
-            Rw = torch.zeros(M + 2, d + 8, dtype=BF16, device="cuda")
-            Rw[:M, :d] = f(R)
-            a_in, r_in = Aw[:, 32:32 + d], Rw[:M, :d]
+            a_in, r_in = GI(A, pad_cols=(32, 32)), GI(R, pad_cols=(0, 8))      # strided operand views, NaN around them
         else:
             ch = chains.Chain(None, len(blocks("cpu")), blocks("cpu"))
             a_in, r_in = A, R
@@ -1340,6 +1609,7 @@ def test_row_chain_matches_the_separate_kernels(M, variant):
         return o
 
     split_work = torch.zeros(nv.split_work_words(), dtype=torch.int32, device="cuda") if "split" in parts else None
+    guards = []
     got, ref = run("cuda", nv.row_chain, dn1, dn2), run("cpu", em.row_chain, de1, de2)
     if split_work is not None:
         # the tickets are back at zero, and a second launch on the same scratch gives bit-identical results (the partials are
@@ -1347,7 +1617,7 @@ def test_row_chain_matches_the_separate_kernels(M, variant):
         assert int(split_work[:256].abs().sum()) == 0, "split tickets not reset"
         again = run("cuda", nv.row_chain, dn1, dn2)
         for n in got:
-            assert torch.equal(got[n], again[n]), "split row chain not reproducible: %s" % n
+            assert same_bits(got[n], again[n]), "split row chain not reproducible: %s" % n
         if M == 5:      # the same scratch after a launch with more row blocks (whose partials lie where nothing else may)
             M_big = 320
             chains_mod = chains
@@ -1364,10 +1634,14 @@ def test_row_chain_matches_the_separate_kernels(M, variant):
                          post=(nb, cu(bp), Eb(M_big, 256 * max(nb, 1))) if nb else None)
             again = run("cuda", nv.row_chain, dn1, dn2)
             for n in got:
-                assert torch.equal(got[n], again[n]), "split row chain after a larger launch on the same scratch: %s" % n
+                assert same_bits(got[n], again[n]), "split row chain after a larger launch on the same scratch: %s" % n
     names = (["out0", "xhat0", "rstd0"] if has_pre else []) + (["H", "out1", "xhat1", "rstd1"] if has_ffn else []) + (["P"] if nb else [])
     for n in names:
-        check(got[n], ref[n], 2e-3 if n.startswith("rstd") else 1e-2, "row_chain %s M=%d: %s" % (variant, M, n))
+        check(got[n], ref[n], 2e-3 if n.startswith("rstd") else 1e-2, "row_chain %s M=%d: %s" % (variant, M, n),
+              tol_local=L_F32 if n.startswith("rstd") else L_BF16)
+    for gd in guards:       # (outputs the variant does not produce included: nothing reaches them or their surroundings)
+        for n in gd:
+            gd[n].assert_intact("row_chain %s M=%d: %s" % (variant, M, n))
     if has_ffn:      # the ReLU-mask bits the backward chain will read == the bits of the H the same launch wrote
         want = nv.relu_bits_from(got["H"])
         diff = got["bits"] ^ want
@@ -1408,15 +1682,14 @@ def test_row_chain512_matches_the_separate_kernels(M, variant):
         o = dict(out0=E(M, d), xhat0=E(M, d), rstd0=E(M, dt=F32), H=E(M, dff), out1=E(M, d), xhat1=E(M, d), rstd1=E(M, dt=F32), P=E(M, 3 * d))
         blocks = chains.encoder512_blocks(f(wo), f(w1), f(w2), f(wp) if post else None)
         if dev == "cuda":
+            gd = _chain_fwd_guards(M, d, dff, 3 * d)
+            guards.append(gd)
+            o = {k: v.view for k, v in gd.items()}
             cs = chains.ChainSet("cuda")
             cid = cs.add(blocks)
             cs.finalize().rebuild()
             ch = cs.chain(cid)
-            Aw = torch.zeros(M, d + 64, dtype=BF16, device="cuda")      # strided operand views
-            Aw[:, 32:32 + d] = f(A)
-            Rw = torch.zeros(M + 2, d + 8, dtype=BF16, device="cuda")
-            Rw[:M, :d] = f(R)
-            a_in, r_in = Aw[:, 32:32 + d], Rw[:M, :d]
+            a_in, r_in = GI(A, pad_cols=(32, 32)), GI(R, pad_cols=(0, 8))      # strided operand views, NaN around them
             o["bits"] = torch.zeros(nv.chain_mask_words(M, dff, d), dtype=torch.int64, device=dev)
         else:
             ch = chains.Chain(None, len(blocks), blocks)
@@ -1426,9 +1699,13 @@ def test_row_chain512_matches_the_separate_kernels(M, variant):
            post=(6, f(bp), o["P"]) if post else None, **({"post_kscale": 0.125 * nv.K_LOG2_SCALE} if "ks" in parts else {}))
         return o
 
+    guards = []
     got, ref = run("cuda", nv.row_chain, dn1, dn2), run("cpu", em.row_chain, de1, de2)
     for n in ["out0", "xhat0", "rstd0", "H", "out1", "xhat1", "rstd1"] + (["P"] if post else []):
-        check(got[n], ref[n], 2e-3 if n.startswith("rstd") else 1e-2, "row_chain512 %s M=%d: %s" % (variant, M, n))
+        check(got[n], ref[n], 2e-3 if n.startswith("rstd") else 1e-2, "row_chain512 %s M=%d: %s" % (variant, M, n),
+              tol_local=L_F32 if n.startswith("rstd") else L_BF16)
+    for n in guards[0]:
+        guards[0][n].assert_intact("row_chain512 %s M=%d: %s" % (variant, M, n))
     want = nv.relu_bits_from(got["H"], d)
     diff = got["bits"] ^ want
     nc, n_wg = dff // 256, want.numel() // (dff // 256 * 512)
@@ -1479,7 +1756,10 @@ def test_attn_f1_fwd_equals_row_chain_plus_attn_fwd(case):
         E = lambda *s, dt=BF16: torch.zeros(*s, dtype=dt, device="cuda")
         return dict(out=E(M, d), xhat=E(M, d), rstd=E(M, dt=F32), q=E(M, d), O=E(M, d), ores=E(M, d), lse=E(H * M, dt=F32))
 
-    a, b = bufs(), bufs()
+    # the fused launch writes into guarded buffers (packed layout: every row is written; out / xhat / ores have fixed leading dimensions)
+    gd = dict(out=GO(M, d, contiguous=True), xhat=GO(M, d, contiguous=True), rstd=GV(M), q=GO(M, d), O=GO(M, d, contiguous=True),
+              ores=GO(M, d, contiguous=True), lse=GV(H * M))
+    a, b = bufs(), {k: v.view for k, v in gd.items()}
     nv.row_chain(A, ch, pre=(R, bo, g0, be0, a["out"], a["xhat"], a["rstd"]), post=(1, bq, a["q"]))
     nv.attn_fwd(a["q"], kv[:, :d], kv[:, d:], a["O"], a["lse"], q_rows.off, q_rows.len, k_rows.off, k_rows.len, H, int(q_len.max()),
                 False, scale, work=work, drop=drop, max_k=int(k_len.max()), ores=a["ores"])
@@ -1489,6 +1769,7 @@ def test_attn_f1_fwd_equals_row_chain_plus_attn_fwd(case):
     torch.cuda.synchronize()
     for n in a:
         assert torch.equal(a[n], b[n]), "attn_f1_fwd %s: %s differs (max |d| %.3e)" % (case, n, (a[n].float() - b[n].float()).abs().max().item())
+        gd[n].assert_intact("attn_f1_fwd %s: %s" % (case, n))
     assert float(b["O"].float().abs().sum()) > 0
 
 
@@ -1528,7 +1809,9 @@ def test_attn_sf1_fwd_equals_the_three_launches(case):
         return dict(ctx=E(M, d), ores_s=E(M, d), lse_s=E(H * M, dt=F32), out=E(M, d), xhat=E(M, d), rstd=E(M, dt=F32), q=E(M, d),
                     O=E(M, d), ores=E(M, d), lse=E(H * M, dt=F32))
 
-    a, b = bufs(), bufs()
+    C = lambda: GO(M, d, contiguous=True)
+    gd = dict(ctx=C(), ores_s=C(), lse_s=GV(H * M), out=C(), xhat=C(), rstd=GV(M), q=GO(M, d), O=C(), ores=C(), lse=GV(H * M))
+    a, b = bufs(), {k: v.view for k, v in gd.items()}
     nv.attn_fwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], a["ctx"], a["lse_s"], q_rows.off, q_rows.len, q_rows.off, q_rows.len, H, mq,
                 True, scale, work=w_self, drop=d_self, max_k=mq, ores=a["ores_s"])
     nv.row_chain(a["ctx"], ch, pre=(R, bo, g0, be0, a["out"], a["xhat"], a["rstd"]), post=(1, bq, a["q"]))
@@ -1539,6 +1822,7 @@ def test_attn_sf1_fwd_equals_the_three_launches(case):
                     drop_self=d_self, drop=d_cross, max_k=mk, ores_self=b["ores_s"], ores=b["ores"])
     torch.cuda.synchronize()
     for n in a:
+        gd[n].assert_intact("attn_sf1_fwd %s: %s" % (case, n))
         if n == "ores_s":
             # the self-attention's bf16 RESIDUAL of the context (what bf16 rounding dropped: O + Ores = the fp32 context to ~16 bits):
             # the fused stage reproduces the context and the LSE bit for bit, its fp32 context agrees to a few 1e-6 relative (it shows
@@ -1590,6 +1874,9 @@ def test_row_chain_bwd_matches_the_separate_kernels(M, variant):
         o = dict(ds_a=Z(M, d), dga=Z(d, dt=F32) + 1, dba=Z(d, dt=F32) + 2, dbia=Z(d, dt=F32) + 3, dH=Z(M, dff), ds_b=Z(M, d),
                  dgb=Z(d, dt=F32) - 1, dbb=Z(d, dt=F32) - 2, dbib=Z(d, dt=F32) - 3, dctx=Z(M, d), delta=Z(4 * M, dt=F32))
         if dev == "cuda":
+            gd = _chain_bwd_guards(M, d, dff, 4)
+            guards.append(gd)
+            o = {k: v.view for k, v in gd.items()}
             cs = chains.ChainSet("cuda")
             cid = cs.add(blocks(f))
             cs.finalize().rebuild()
@@ -1607,17 +1894,21 @@ def test_row_chain_bwd_matches_the_separate_kernels(M, variant):
         return o
 
     split_work = torch.zeros(nv.split_work_words(), dtype=torch.int32, device="cuda") if "split" in parts else None
-    got, ref = run("cuda", nv.row_chain_bwd, dn), run("cpu", em.row_chain_bwd, de)
+    guards = []
+    got, ref = run("cuda", nv.row_chain_bwd, dn), run("cpu", functools.partial(em.row_chain_bwd, dbias_rounded=True), de)
     if split_work is not None:
         assert int(split_work[:256].abs().sum()) == 0, "split tickets not reset"
         again = run("cuda", nv.row_chain_bwd, dn)
         for n in ("ds_a", "dH", "ds_b", "dctx", "delta"):       # (the column sums are atomic adds: order-dependent rounding)
-            assert torch.equal(got[n], again[n]), "split backward row chain not reproducible: %s" % n
+            assert same_bits(got[n], again[n]), "split backward row chain not reproducible: %s" % n
     names = (["ds_a", "dga", "dba", "dbia"] if has_head else []) + (["dH", "ds_b", "dgb", "dbb", "dbib"] if has_ffn else []) + \
         (["dctx", "delta"] if has_tail else [])
     for n in names:
         tol = 1e-2 if got[n].dtype == BF16 else 5e-3
-        check(got[n], ref[n], tol, "row_chain_bwd %s M=%d: %s" % (variant, M, n))
+        check(got[n], ref[n], tol, "row_chain_bwd %s M=%d: %s" % (variant, M, n), tol_local=L_CHAIN_BWD[n])
+    for gd in guards:
+        for n in gd:
+            gd[n].assert_intact("row_chain_bwd %s M=%d: %s" % (variant, M, n))
 
 
 @pytest.mark.parametrize("n", [4, 1000, 13_300_004, 4 * 1024 * 2048 * 4 + 12])
@@ -1653,14 +1944,17 @@ def test_row_chain_bwd_column_sums_through_the_workspace(M):
     ga, gb = c(g(d, seed=12, dtype=F32) * 0.2 + 1), c(g(d, seed=13, dtype=F32) * 0.2 + 1)
     bits = nv.relu_bits_from(torch.relu(c(g(M, dff, seed=14))))
     O, Ores = c(g(M, d, seed=15)), c(g(M, d, seed=16, scale=2.0 ** -9))
-    E = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device="cuda")
-
     def run(deferred):
-        acc = [torch.full((d,), float(i), device="cuda") for i in range(6)]
+        gd = _chain_bwd_guards(M, d, dff, 4)
+        names = ("dga", "dba", "dbia", "dgb", "dbb", "dbib")
+        for i, n in enumerate(names):
+            gd[n].view.fill_(float(i))
+        acc = [gd[n].view for n in names]
         nv.fold_deferred = deferred
         try:
-            nv.row_chain_bwd(ch, M, head=(3, dP, G, xa, ra, ga, None, E(M, d), acc[0], acc[1], acc[2]),
-                             ffn=(dff, bits, 1.0, E(M, dff), xb, rb, gb, E(M, d), acc[3], acc[4], acc[5]), tail=(O, Ores, E(M, d), E(4 * M, dt=F32)))
+            nv.row_chain_bwd(ch, M, head=(3, dP, G, xa, ra, ga, None, gd["ds_a"].view, acc[0], acc[1], acc[2]),
+                             ffn=(dff, bits, 1.0, gd["dH"].view, xb, rb, gb, gd["ds_b"].view, acc[3], acc[4], acc[5]),
+                             tail=(O, Ores, gd["dctx"].view, gd["delta"].view))
             if deferred:
                 torch.cuda.synchronize()
                 for i in range(6):
@@ -1671,6 +1965,9 @@ def test_row_chain_bwd_column_sums_through_the_workspace(M):
         finally:
             nv.fold_deferred = False
         torch.cuda.synchronize()
+        for n in gd:
+            gd[n].assert_intact("row_chain_bwd through the workspace, M=%d: %s" % (M, n))
+            assert bool(torch.isfinite(gd[n].view.float()).all()), n
         return acc
 
     a, b, c2 = run(False), run(True), run(False)
@@ -1706,6 +2003,9 @@ def test_row_chain512_bwd_matches_the_separate_kernels(M, variant):
                  dgb=Z(d, dt=F32) - 1, dbb=Z(d, dt=F32) - 2, dbib=Z(d, dt=F32) - 3, dctx=Z(M, d), delta=Z(8 * M, dt=F32))
         blocks = chains.encoder512_blocks_bwd(f(wo), f(w1), f(w2), f(wp) if nb else None)
         if dev == "cuda":
+            gd = _chain_bwd_guards(M, d, dff, 8)
+            guards.append(gd)
+            o = {k: v.view for k, v in gd.items()}
             cs = chains.ChainSet("cuda")
             cid = cs.add(blocks)
             cs.finalize().rebuild()
@@ -1719,10 +2019,12 @@ def test_row_chain512_bwd_matches_the_separate_kernels(M, variant):
            tail=(f(O), None if nores else f(Ores), o["dctx"], o["delta"]))
         return o
 
-    got, ref = run("cuda", nv.row_chain_bwd, dn), run("cpu", em.row_chain_bwd, de)
+    guards = []
+    got, ref = run("cuda", nv.row_chain_bwd, dn), run("cpu", functools.partial(em.row_chain_bwd, dbias_rounded=True), de)
     for n in ["ds_a", "dga", "dba", "dbia", "dH", "ds_b", "dgb", "dbb", "dbib", "dctx", "delta"]:
         tol = 1e-2 if got[n].dtype == BF16 else 5e-3
-        check(got[n], ref[n], tol, "row_chain512_bwd %s M=%d: %s" % (variant, M, n))
+        check(got[n], ref[n], tol, "row_chain512_bwd %s M=%d: %s" % (variant, M, n), tol_local=L_CHAIN512_BWD[n])
+        guards[0][n].assert_intact("row_chain512_bwd %s M=%d: %s" % (variant, M, n))
 
 
 @pytest.mark.parametrize("two_launch", [False, True])
@@ -1835,7 +2137,7 @@ def test_cross_entropy_rows_matches_torch(R, V):
     assert abs(loss.item() - ref.item()) < 1e-5 * abs(ref.item())
     if vp > V:      # (autograd casts the bf16 gradient to the leaf's fp32; functional.VocabCeFn consumes it as bf16)
         assert float(x.grad[:, V:].abs().max()) == 0.0
-    check(x.grad[:, :V], ref_in.grad, 6e-3, "cross-entropy gradient")
+    check(x.grad[:, :V], ref_in.grad, 6e-3, "cross-entropy gradient", tol_local=L_CE)
     assert float(x.grad[::5].abs().max()) == 0.0
     # the indexed form (row r's target = truth[index[r]]: the padded ground truth read through the ragged rows' positions)
     # against the gathered form: same kernels, same bits
@@ -1845,32 +2147,40 @@ def test_cross_entropy_rows_matches_torch(R, V):
     lg = logits.cuda()
     outs = []
     for tgt, index in ((target.cuda(), None), (truth.cuda(), idx.cuda())):
-        lse, sums = torch.empty(R, device="cuda"), torch.empty(3, device="cuda")
+        gl, gs, gdl = GV(R), GV(3), GO(R, vp, contiguous=True)
+        lse, sums, dl = gl.view, gs.view, gdl.view
         nv.ce_fwd(lg, tgt, 0, lse, sums, index=index)
-        dl = torch.empty(R, vp, dtype=BF16, device="cuda")
         nv.ce_bwd(lg, tgt, 0, lse, sums, torch.ones(1, device="cuda"), dl, index=index)
+        for gd_, nm in ((gl, "lse"), (gs, "sums"), (gdl, "dlogits")):
+            gd_.assert_intact("cross-entropy %s" % nm)
         outs.append((lse, sums, dl))
     for a, b in zip(*outs):
         assert torch.equal(a, b)
+    check(outs[0][0], torch.logsumexp(logits[:, :V].double(), -1), 2e-3, "cross-entropy lse", tol_local=L_F32)
+    check(outs[0][2][:, :V], ref_in.grad / 0.7, 6e-3, "cross-entropy gradient (raw kernels)", tol_local=L_CE)
+    assert float(outs[0][2][:, V:].float().abs().max()) == 0.0 if vp > V else True
     assert abs(float(outs[0][1][2]) - ref.item()) < 1e-5 * abs(ref.item())
 
 
 @pytest.mark.parametrize("lineage", [False, True])
-@pytest.mark.parametrize("t", [0, 1, 15, 16, 37, 63, 64, 99])
+@pytest.mark.parametrize("t", [0, 1, 15, 16, 37, 63, 64, 99, 127])      # 127: with S = 128, the documented maximum
 def test_decode_self_attention_matches_reference(t, lineage):
     """st_decode_self_attn (one query per hypothesis over the KV cache, appending this step's K | V) == the fp32 softmax
     attention over cache positions 0 .. t, for positions inside and beyond the first 64-key pass; with a lineage table
     the earlier positions come from the cache rows it names (random rows here), the step's own from the hypothesis' row."""
-    n, H, d, S = 37, 4, 256, 100
+    n, H, d, S = 37, 4, 256, (128 if t == 127 else 100)
     qkv = g(n, 3 * d, seed=1)
     cache = g(n, S, 2 * d, seed=2)
     step = torch.tensor([t], dtype=torch.long)
     anc = torch.randint(0, n, (n, S), generator=torch.Generator().manual_seed(5), dtype=torch.int32) if lineage else None
-    cg, ce = cache.clone().cuda(), cache.clone()
-    out_g, out_e = torch.zeros(n, d, dtype=BF16, device="cuda"), torch.zeros(n, d, dtype=BF16)
-    nv.decode_self_attn(cu(qkv), cg, step.cuda(), out_g, H, 0.125, anc=anc.cuda() if lineage else None)
+    gc, go = GO(n * S, 2 * d, contiguous=True, shape=(n, S, 2 * d)), GO(n, d)
+    gc.view.copy_(cache)
+    cg, ce = gc.view, cache.clone()
+    out_g, out_e = go.view, torch.zeros(n, d, dtype=BF16)
+    nv.decode_self_attn(GI(qkv), cg, step.cuda(), out_g, H, 0.125, anc=anc.cuda() if lineage else None)
     em.decode_self_attn(qkv, ce, step, out_e, H, 0.125, anc=anc)
-    check(out_g, out_e, 1e-2, "decode self-attention t=%d" % t)
+    check(out_g, out_e, 1e-2, "decode self-attention t=%d" % t, tol_local=L_BF16)
+    gc.assert_intact("decode self-attention t=%d: cache" % t), go.assert_intact("decode self-attention t=%d: context" % t)
     assert torch.equal(cg.cpu()[:, t], qkv[:, d:]) and torch.equal(cg.cpu()[:, t + 1:], cache[:, t + 1:]) and \
         torch.equal(cg.cpu()[:, :t], cache[:, :t])
 
@@ -1903,11 +2213,17 @@ def test_ctc_gather_and_dlogits_kernels(V, lens, C):
         mv = lambda t: t.to(dev)
         lse = torch.zeros(R, dtype=F32, device=dev)
         lp = torch.zeros(B, T, C, dtype=F32, device=dev)
-        mod.ctc_gather(mv(logits), mv(rowmap), T, mv(cols), lse, lp, V=V)
         dl = torch.full((R, v_pad), 7.0, dtype=BF16, device=dev)
+        if dev == "cuda":
+            gl, gdl = GV(R), GO(R, v_pad, contiguous=True)
+            lse, dl = gl.view, gdl.view
+        mod.ctc_gather(mv(logits), mv(rowmap), T, mv(cols), lse, lp, V=V)
         mod.ctc_dlogits(mv(logits), lse, mv(rowmap), T, mv(roww), mv(scat), mv(gsmall), mv(gout), dl, V=V)
         outs.append((lse.cpu(), lp.cpu(), dl.float().cpu()))
+    gl.assert_intact("ctc_gather lse"), gdl.assert_intact("ctc_dlogits")
     (l0, p0, d0), (l1, p1, d1) = outs
+    check(l1, l0, 2e-3, "ctc_gather lse", tol_local=L_F32)
+    check(d1[:, :V], d0[:, :V], 1e-2, "ctc_dlogits", tol_local=L_BF16)
     assert torch.allclose(l0, l1, rtol=0, atol=2e-5), float((l0 - l1).abs().max())
     assert torch.allclose(p0, p1, rtol=0, atol=3e-5), float((p0 - p1).abs().max())
     assert float((d0[:, :V] - d1[:, :V]).abs().max()) <= 1e-2 * float(d0[:, :V].abs().max()) + 1e-6
