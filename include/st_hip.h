@@ -616,6 +616,49 @@ int stx_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, i
                       const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
                       const float* denom, const float* lse, const float* sums, const float* grad_out, void* dlogits, int ldd);
 
+/* ---- Second extension section ------------------------------------------------------------------------------------------
+ * The stx_ section above is pinned from outside this header in the same way as the base section (its names and its version
+ * number are spelled out by the tests that came with it).  This section - prefix `st2_`, version ST2_VERSION returned by
+ * st2_version() - is checked DIFFERENTLY: its test derives the expected set from this header and compares it with the binding
+ * (native.EXT2_SIGNATURES, parsed by the same native.parse_extension with prefix "st2"), with the library's exported
+ * symbols and with the extern "C" definitions under csrc/.  So the NEXT entry point is declared here and ST2_VERSION is
+ * bumped; no further prefix is needed.  Conventions, library and return codes are those of the two sections above.
+ *
+ * SpecAugment (Park et al. 2019: time and frequency masks; the time warp is not built) inside the training step.  Masks are
+ * drawn per utterance from the dropout seed in device memory (drop_seed above), so a captured graph draws new masks on every
+ * replay; they are applied by the kernel that converts the features to bf16 rows anyway, so no extra byte moves.
+ *
+ * The draw (integers only).  key = hash32(*seed + salt * 0x9e3779b9), hash32 = the dropout hash of csrc/st_common.cuh.  For
+ * utterance b, mask j (time masks j = 0 .. n_time - 1, then the frequency masks) and draw d in {0, 1}:
+ *   bits_d = hash32(((b * 64 + j) * 2 + d) ^ key),      pick(bits, n) = (uint64(bits) * n) >> 32
+ *   time mask:       cap = min(time_width, T_raw * time_ratio_permille / 1000)   (integer division)
+ *                    width = pick(bits_0, cap + 1),  start = pick(bits_1, T_raw - width + 1)
+ *   frequency mask:  cap = min(freq_width, mel_bins),  width = pick(bits_0, cap + 1),  start = pick(bits_1, mel_bins - width + 1)
+ * Width 0 = no mask; masked elements become 0.0 (the mean after CMVN).  Masks live in RAW coordinates: frames of the
+ * unstacked utterance, bins of one raw frame.
+ *
+ * st2_specaug_plan: table int32 [B, n_time + n_freq, 2] = (start, width) of every mask of every utterance, one small launch.
+ * T_raw = (len[b] - 1) * interval + 1 + right (0 when len[b] < 1) with len on the DEVICE: pass (interval 1, right 0) with raw
+ * lengths, or the stacking geometry with the lengths of already stacked / subsampled rows - then T_raw is the last raw frame
+ * that can appear in a row, plus one.  n_time + n_freq <= 64. */
+#define ST2_VERSION 1
+int st2_version(void);
+int st2_specaug_plan(st_stream_t stream, const unsigned* seed, unsigned salt, const int* len, int B, int interval, int right,
+                     int n_time, int time_width, int time_ratio_permille, int n_freq, int freq_width, int mel_bins, int* table);
+/* st_pack_rows with the masks of `table` applied: x fp32 [B, T, F], F = mel_bins * (1 + left + right), rows ALREADY stacked /
+ * subsampled as st_feat_stack would (left = right = 0, interval = 1: plain frames).  Column c = context slot k = c / mel_bins,
+ * bin f = c % mel_bins; row r, slot k hold raw frame src(k, r * interval) by st_feat_stack's rule (csrc/st_augment.cuh) with
+ * the utterance's T_raw (as st2_specaug_plan computes it) for the raw length - the true raw length is not known here, so a
+ * right-context slot that the reference's right-width indexing lays over another slot counts as the right context.  An
+ * element is zeroed iff its source frame lies in a time mask or its bin in a frequency mask.  mel_bins % 4 == 0. */
+int st2_pack_rows_aug(st_stream_t stream, const float* x, int B, int T, int F, const int* off, const int* len, void* out,
+                      const int* table, int n_time, int n_freq, int mel_bins, int left, int right, int interval);
+/* st_feat_stack with the masks of `table` (planned with the raw lengths in_len, interval 1, right 0; mel_bins = F) applied
+ * after CMVN and before stacking. */
+int st2_feat_stack_aug(st_stream_t stream, const float* x, int B, int T, int F, const int* in_len, const float* stats, int left,
+                       int right, int interval, const int* out_off, const int* out_len, int max_out_len, void* out, int ld,
+                       const int* table, int n_time, int n_freq);
+
 #ifdef __cplusplus
 }
 #endif

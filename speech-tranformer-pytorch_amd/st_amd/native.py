@@ -53,15 +53,16 @@ def parse_header(text: str):
     return sigs, int(version.group(1)), epi
 
 
-def parse_extension(text: str):
-    """-> (EXT_SIGNATURES: name -> argtypes of every ``int stx_*(...);`` declaration, STX_VERSION) of the header's extension
-    section: the entry points added after the base ABI was frozen (the section's comment in include/st_hip.h says why they
+def parse_extension(text: str, prefix: str = "stx"):
+    """-> (name -> argtypes of every ``int <prefix>_*(...);`` declaration, <PREFIX>_VERSION) of one of the header's extension
+    sections: the entry points added after the base ABI was frozen (the sections' comments in include/st_hip.h say why they
     are kept apart).  Same parameter rules as parse_header."""
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    sigs = {name: _argtypes(name, params) for name, params in re.findall(r"\bint\s+(stx_\w+)\s*\(([^)]*)\)\s*;", text)}
-    version = re.search(r"#define\s+STX_VERSION\s+(\d+)", text)
+    sigs = {name: _argtypes(name, params)
+            for name, params in re.findall(r"\bint\s+(%s_\w+)\s*\(([^)]*)\)\s*;" % re.escape(prefix), text)}
+    version = re.search(r"#define\s+%s_VERSION\s+(\d+)" % re.escape(prefix.upper()), text)
     if not sigs or version is None:
-        raise RuntimeError("include/st_hip.h: no stx_* declarations / STX_VERSION found: broken checkout")
+        raise RuntimeError("include/st_hip.h: no %s_* declarations / %s_VERSION found: broken checkout" % (prefix, prefix.upper()))
     return sigs, int(version.group(1))
 
 
@@ -79,6 +80,8 @@ def _read_header() -> str:
 SIGNATURES, ABI_VERSION, _EPI = parse_header(_read_header())
 # ... and the same for the header's extension section (the stx_* entry points)
 EXT_SIGNATURES, EXT_VERSION = parse_extension(_read_header())
+# ... and its second extension section (st2_*: SpecAugment)
+EXT2_SIGNATURES, EXT2_VERSION = parse_extension(_read_header(), "st2")
 (EPI_BF16, EPI_BF16_RELU, EPI_F32, EPI_BF16_MASK, EPI_BF16_ADD, EPI_F32_ATOMIC, EPI_F32_ATOMIC_T, EPI_BF16_DELTA) = (
     _EPI["ST_" + k] for k in ("EPI_BF16", "EPI_BF16_RELU", "EPI_F32", "EPI_BF16_MASK", "EPI_BF16_ADD", "EPI_F32_ATOMIC",
                               "EPI_F32_ATOMIC_T", "EPI_BF16_DELTA"))
@@ -181,19 +184,21 @@ def load(build_if_missing: bool = True):
     if ver != ABI_VERSION:
         raise RuntimeError("libst_hip.so at %s has ABI version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
                            % (path, ver, ABI_VERSION))
-    try:
-        cdll.stx_version.restype = _c_int
-        xver = int(cdll.stx_version())
-    except AttributeError:
-        xver = -1
-    if xver != EXT_VERSION:
-        raise RuntimeError("libst_hip.so at %s has extension version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
-                           % (path, xver, EXT_VERSION))
-    missing = [name for name in list(SIGNATURES) + list(EXT_SIGNATURES) if not hasattr(cdll, name)]
+    for entry, want, what in (("stx_version", EXT_VERSION, "extension"), ("st2_version", EXT2_VERSION, "second extension")):
+        try:
+            getattr(cdll, entry).restype = _c_int
+            xver = int(getattr(cdll, entry)())
+        except AttributeError:
+            xver = -1
+        if xver != want:
+            raise RuntimeError("libst_hip.so at %s has %s version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
+                               % (path, what, xver, want))
+    bound = list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT2_SIGNATURES.items())
+    missing = [name for name, _ in bound if not hasattr(cdll, name)]
     if missing:
         raise RuntimeError("libst_hip.so at %s lacks %s: rebuild it (python __graft_entry__.py)" % (path, ", ".join(missing)))
     lib = _Lib()
-    for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, argtypes in bound:
         fn = getattr(cdll, name)
         fn.argtypes = argtypes
         fn.restype = _c_int
@@ -1144,6 +1149,84 @@ def feat_stack(x, in_len, stats, left, right, interval, out_off, out_len, max_ou
                               int(interval), out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(),
                               out.stride(0))
     _check(rc, "st_feat_stack")
+    return out
+
+
+def _specaug_args(who, n_time, n_freq, left, right, interval):
+    """The integer checks the three SpecAugment wrappers share (before any tensor is looked at): mask counts and stacking geometry."""
+    n_time, n_freq, left, right, interval = int(n_time), int(n_freq), int(left), int(right), int(interval)
+    if n_time < 0 or n_freq < 0 or n_time + n_freq > 64:
+        raise ValueError("%s: %d time + %d frequency masks - both counts >= 0 and at most 64 masks in all" % (who, n_time, n_freq))
+    if left < 0 or right < 0 or right > left or interval < 1:
+        raise ValueError("%s: left %d / right %d / interval %d - contexts >= 0, right <= left, interval >= 1" % (who, left, right, interval))
+    return n_time, n_freq, left, right, interval
+
+
+def specaug_plan(seed, salt, length, table, n_time, time_width, time_ratio_permille, n_freq, freq_width, mel_bins, interval=1,
+                 right=0):
+    """SpecAugment's masks of one step (st2_specaug_plan): table int32 [B, n_time + n_freq, 2] <- (start, width) of every
+    mask, drawn from the device seed (the 1-element int32 tensor of st_amd.rng) and ``salt``.  length: int32 [B] on the device
+    - raw frames with (interval 1, right 0), else rows already stacked with that geometry."""
+    B = length.numel()
+    if min(int(time_width), int(freq_width)) < 0 or int(mel_bins) < 1 or not 0 <= int(time_ratio_permille) <= 1000:
+        raise ValueError("specaug_plan: time_width %d / freq_width %d >= 0, mel_bins %d >= 1, time_ratio_permille %d in 0 .. 1000"
+                         % (time_width, freq_width, mel_bins, time_ratio_permille))
+    if B > 1 << 24:
+        raise ValueError("specaug_plan: at most 2^24 utterances (the draw's counter is 32 bits wide)")
+    n_time, n_freq, _, right, interval = _specaug_args("specaug_plan", n_time, n_freq, right, right, interval)
+    _dev(table, I32, (B, n_time + n_freq, 2), "specaug_plan: table")
+    _dev(seed, I32, (1,), "specaug_plan: seed"), _vec(length, I32, B, "specaug_plan: length")
+    _tag("specaug_plan", B, n_time + n_freq, io=(length, table))
+    _check(load().st2_specaug_plan(_stream(), seed.data_ptr(), int(salt) & 0xFFFFFFFF, length.data_ptr(), B, interval, right, n_time,
+                                   int(time_width), int(time_ratio_permille), n_freq, int(freq_width), int(mel_bins),
+                                   table.data_ptr()), "st2_specaug_plan")
+    return table
+
+
+def pack_rows_aug(x, off, length, out, table, n_time, n_freq, mel_bins, left=0, right=0, interval=1):
+    """pack_rows with the masks of ``table`` applied (st2_pack_rows_aug): x fp32 [B, T, mel_bins * (1 + left + right)], rows
+    already stacked / subsampled with that geometry."""
+    if x.dim() != 3:
+        raise ValueError("pack_rows_aug: x must be [B, T, F], got %s" % (tuple(x.shape),))
+    B, T, Fd = x.shape
+    mel_bins = int(mel_bins)
+    if mel_bins < 4 or mel_bins % 4:
+        raise ValueError("pack_rows_aug: mel_bins = %d must be a positive multiple of 4 (a 16-byte chunk lies in one context slot)" % mel_bins)
+    n_time, n_freq, left, right, interval = _specaug_args("pack_rows_aug", n_time, n_freq, left, right, interval)
+    if Fd != mel_bins * (1 + left + right):
+        raise ValueError("pack_rows_aug: %d columns are not %d bins x (1 + %d + %d) context slots" % (Fd, mel_bins, left, right))
+    _dev(table, I32, (B, n_time + n_freq, 2), "pack_rows_aug: table")
+    _dev(x, F32, (B, T, Fd), "pack_rows_aug: x")
+    _vec(off, I32, B, "off"), _vec(length, I32, B, "len")
+    if off.numel() != B or length.numel() != B:
+        raise ValueError("pack_rows_aug: off / len must have one entry per utterance (%d)" % B)
+    _mat(out, BF16, "out", ld=Fd)
+    _tag("pack_rows_aug", out.shape[0], Fd, io=(float(out.shape[0]) * Fd * x.element_size(), out, table))
+    _check(load().st2_pack_rows_aug(_stream(), x.data_ptr(), B, T, Fd, off.data_ptr(), length.data_ptr(), out.data_ptr(),
+                                    table.data_ptr(), n_time, n_freq, mel_bins, left, right, interval), "st2_pack_rows_aug")
+    return out
+
+
+def feat_stack_aug(x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out, table, n_time, n_freq):
+    """feat_stack with the masks of ``table`` (planned with the raw lengths) applied after CMVN, before stacking
+    (st2_feat_stack_aug)."""
+    if x.dim() != 3:
+        raise ValueError("feat_stack_aug: x must be [B, T, F], got %s" % (tuple(x.shape),))
+    B, T, F = x.shape
+    n_time, n_freq, left, right, interval = _specaug_args("feat_stack_aug", n_time, n_freq, left, right, interval)
+    _dev(table, I32, (B, n_time + n_freq, 2), "feat_stack_aug: table")
+    _dev(x, F32, (B, T, F), "feat_stack_aug: x")
+    _vec(in_len, I32, B, "in_len"), _vec(out_off, I32, B, "out_off"), _vec(out_len, I32, B, "out_len")
+    _mat(out, BF16, "out")
+    if out.stride(0) < F * (1 + left + right):
+        raise ValueError("feat_stack_aug: out has a leading dimension of %d for %d stacked columns" % (out.stride(0), F * (1 + left + right)))
+    if stats is not None:
+        _dev(stats, F32, (B, 2, F + 1), "feat_stack_aug: stats")
+    _tag("feat_stack_aug", B, T, F)
+    rc = load().st2_feat_stack_aug(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), left, right, interval,
+                                   out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(), out.stride(0),
+                                   table.data_ptr(), n_time, n_freq)
+    _check(rc, "st2_feat_stack_aug")
     return out
 
 

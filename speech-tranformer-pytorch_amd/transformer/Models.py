@@ -43,6 +43,9 @@ class Encoder(nn.Module):
         self.layer_stack = nn.ModuleList([
             EncoderLayer(d_model, d_inner_hid, n_head, d_k, d_v, dropout=dropout) for _ in range(n_layers)])
         self.use_row_chains = True      # False: every GEMM of the layer stack is its own launch (A/B runs, tests)
+        # st_amd.augment.SpecAugment or None: in training mode the padded inputs are masked on their way to bf16 rows (a plain
+        # attribute - no constructor argument, nothing in the state_dict: the reference has neither)
+        self.spec_augment = None
 
     def _st_bind(self, a):
         lin, ln = self.input_proj[0], self.input_proj[3]
@@ -70,7 +73,9 @@ class Encoder(nn.Module):
                     rows = F_.Rows.packed(inputs_length, inputs.device)
             rows.pos                                      # position table built before the first launch
             if packed is None:
-                xp = F_.PackFn.apply(inputs.float(), rows)
+                aug = self.spec_augment if self.training else None
+                # (with a policy: the mask plan + the augmenting pack, two launches where PackFn makes one; no backward)
+                xp = F_.PackFn.apply(inputs.float(), rows) if aug is None else aug.pack(inputs.float(), rows)
             drop = rng.site(xp.device, self.input_proj[2].p) if self.training else None   # Models.py:31: p = 0.5
             e = F_.FrontendFn.apply(xp, self.input_proj[0].weight, self, rows, drop)
             link = None                         # FrontendFn's LayerNorm output is masked/offset: not linked
