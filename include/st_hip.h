@@ -641,7 +641,7 @@ int stx_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, i
  * T_raw = (len[b] - 1) * interval + 1 + right (0 when len[b] < 1) with len on the DEVICE: pass (interval 1, right 0) with raw
  * lengths, or the stacking geometry with the lengths of already stacked / subsampled rows - then T_raw is the last raw frame
  * that can appear in a row, plus one.  n_time + n_freq <= 64. */
-#define ST2_VERSION 1
+#define ST2_VERSION 2
 int st2_version(void);
 int st2_specaug_plan(st_stream_t stream, const unsigned* seed, unsigned salt, const int* len, int B, int interval, int right,
                      int n_time, int time_width, int time_ratio_permille, int n_freq, int freq_width, int mel_bins, int* table);
@@ -658,6 +658,29 @@ int st2_pack_rows_aug(st_stream_t stream, const float* x, int B, int T, int F, c
 int st2_feat_stack_aug(st_stream_t stream, const float* x, int B, int T, int F, const int* in_len, const float* stats, int left,
                        int right, int interval, const int* out_off, const int* out_len, int max_out_len, void* out, int ld,
                        const int* table, int n_time, int n_freq);
+
+/* ---- st2_, version 2: the optimizer update skips non-finite gradients and keeps averaged weights ---------------------------
+ * st_grad_norm with a verdict.  Same grid, same partial sums, same fixed-order fp64 merge: for finite input *gnorm equals
+ * st_grad_norm's value bit for bit.  The workgroup that finishes the reduction is the single writer of the verdict in guard
+ * (device f32 [2]): a finite norm -> *step += 1, guard[0] = 0; otherwise step is left alone, guard[0] = 1 and guard[1] += 1 (a
+ * running count of skipped steps).  *gnorm is written in both cases.  Non-finite: any NaN or +-inf element, and ALSO finite
+ * elements whose sum of squares overflows fp32 within one workgroup's partial sum (the partials are fp32; the norm is then
+ * inf).  step and guard are required; scratch as st_grad_norm (the two may share one). */
+int st2_grad_norm_guard(st_stream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
+                        float grad_scale, float* guard);
+/* st_adam_clip plus two optional behaviours, one kernel body with it (csrc/st_optim.cuh); with found_inf NULL and avg NULL the
+ * results are bit-identical to st_adam_clip.
+ * found_inf (device f32, or NULL): when *found_inf != 0 the launch writes nothing - p, g, m, v and avg keep their bits (g is
+ * NOT clipped or scaled either).  Pass guard of st2_grad_norm_guard.
+ * avg (fp32 [n], or NULL): the exponential moving average of the parameters, updated after the parameter update in the same
+ * pass: avg += w * (p_new - avg), w = 1.0f - d in fp32, d = decay, or with decay_warmup != 0 d = min(decay, (1 + t) / (10 + t))
+ * with t = *step (the count of APPLIED updates, already incremented).  decay in [0, 1]; w == 0 leaves avg untouched. */
+int st2_adam_clip_avg(st_stream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
+                      const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
+                      float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup);
+/* Exchange two fp32 buffers in place (n % 4 == 0, both 16-byte aligned, not overlapping): the averaged weights go under the
+ * model and back.  A pointer swap is not possible - parameter views and captured graphs hold addresses into the arena. */
+int st2_swap_f32(st_stream_t stream, float* a, float* b, long long n);
 
 #ifdef __cplusplus
 }

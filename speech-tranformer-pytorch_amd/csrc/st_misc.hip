@@ -4,6 +4,7 @@
 // feature axis (coalesced 256-512 B per wave per row).
 #include "st_common.cuh"
 #include "st_ce.cuh"
+#include "st_optim.cuh"
 
 namespace {
 
@@ -234,9 +235,6 @@ __global__ void embed_bwd_kernel(const long long* __restrict__ tok, int L, const
   for (int f = threadIdx.x; f < D; f += blockDim.x) atomicAdd(dst + f, (float)src[f]);
 }
 
-#ifndef ST_ADAM_SC1
-#define ST_ADAM_SC1 0
-#endif
 __global__ void cast_bf16_kernel(const float* __restrict__ src, bf16* __restrict__ dst, size_t n8) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
     const f32x4 a = *reinterpret_cast<const f32x4*>(src + i * 8);
@@ -246,105 +244,7 @@ __global__ void cast_bf16_kernel(const float* __restrict__ src, bf16* __restrict
   }
 }
 
-// Global-norm gradient clipping + Adam over the flat parameter arena, one pass (train.py:45-46: clip_grad_norm_ then
-// ScheduledOptim.step; Adam(betas, eps) of transformer/Optim.py).  Same arithmetic as torch's fused Adam kernel
-// (bias corrections from the step count, denom = sqrt(v) / sqrt(bc2) + eps, p -= lr / bc1 * m / denom); the clipped
-// gradient is written back, as clip_grad_norm_ leaves it.  lr / step / gnorm are device scalars, so a captured graph
-// replays with the current learning rate.
-__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, size_t n4, const float* lr_p,
-                                                        const float* step_p, const float* gnorm_p, float max_norm,
-                                                        float beta1, float beta2, float eps, float grad_scale) {
-  const float lr = *lr_p, step = *step_p;
-  // grad_scale: what the buffer still has to be multiplied by to be THE gradient (1 / world behind a summing all-reduce:
-  // the rank average costs no pass of its own); *gnorm_p is the norm of the scaled gradient (st_grad_norm's grad_scale)
-  const float coef = (gnorm_p ? fminf(max_norm / (*gnorm_p + 1e-6f), 1.0f) : 1.0f) * grad_scale;
-  const float bc1 = 1.0f - powf(beta1, step), bc2 = 1.0f - powf(beta2, step);
-  const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2);
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 gg = *reinterpret_cast<const f32x4*>(g + i * 4);
-    f32x4 mm = *reinterpret_cast<const f32x4*>(m + i * 4);
-    f32x4 vv = *reinterpret_cast<const f32x4*>(v + i * 4);
-    f32x4 pp = *reinterpret_cast<const f32x4*>(p + i * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float ge = gg[e] * coef;
-      gg[e] = ge;
-      mm[e] = mm[e] + (1.0f - beta1) * (ge - mm[e]);          // lerp(m, g, 1 - beta1), as torch
-      vv[e] = beta2 * vv[e] + (1.0f - beta2) * ge * ge;
-      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
-      pp[e] -= step_size * mm[e] / denom;
-    }
-    store16<ST_ADAM_SC1>(g + i * 4, gg);
-    store16<ST_ADAM_SC1>(m + i * 4, mm);
-    store16<ST_ADAM_SC1>(v + i * 4, vv);
-    store16<ST_ADAM_SC1>(p + i * 4, pp);
-  }
-}
-
-// Global L2 norm of the flat gradient buffer (clip_grad_norm_'s total_norm, train.py:45) as ONE launch: every workgroup
-// leaves the sum of squares of its grid-stride slice in `partial`, takes a ticket, and the last one adds the partials up (in
-// index order: the result does not depend on the arrival order), writes *gnorm, advances the optimiser's step counter
-// (*step += 1, optional) and resets the ticket for the next launch.  Replaces torch.linalg.vector_norm (52 MB at 2.6 TB/s
-// plus a memset) and the separate step increment: three graph nodes -> one.
-__global__ __launch_bounds__(1024) void grad_norm_kernel(const float* __restrict__ g, size_t n4, float* partial, unsigned* ticket,
-                                                        float* __restrict__ gnorm, float* step, float grad_scale) {
-  __shared__ float red[16];      // 1024 threads x four 16-byte loads in flight = 64 KB per workgroup, 16 MB over the chip
-                                 // (256 threads: 4 MB in flight = ~2 TB/s at ~2 us memory latency: 18 us for 52 MB)
-  __shared__ bool last;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  const size_t stride = (size_t)gridDim.x * 1024;
-  size_t i = blockIdx.x * (size_t)1024 + tid;
-  for (; i + 3 * stride < n4; i += 4 * stride) {      // four 16-byte loads in flight per thread
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(g + (i + u * stride) * 4);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = fmaf(v[u][e], v[u][e], acc[e]);
-  }
-  for (; i < n4; i += stride) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(g + i * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = fmaf(v[e], v[e], acc[e]);
-  }
-  float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-#pragma unroll
-  for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) red[wave] = s;
-  __syncthreads();
-  if (tid == 0) {
-    // write-through store, acknowledged before the ticket is drawn; the last workgroup reads with device-scope loads.  No
-    // fence: an agent-scope release writes the whole L2 back (tools/dev/merge_probe.hip: +60-80 us on 512 workgroups)
-    float bs = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) bs += red[w];
-    __hip_atomic_store(partial + blockIdx.x, bs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    ST_PUBLISH_FENCE();
-    __builtin_amdgcn_s_waitcnt(0);
-    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  ST_MERGER_FENCE();
-  double t = 0.0;
-  if (tid < 256)
-    for (int i = tid; i < (int)gridDim.x; i += 256) t += (double)__hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __shared__ double redd[256];
-  if (tid < 256) redd[tid] = t;
-  __syncthreads();
-  for (int o = 128; o; o >>= 1) {
-    if (tid < o) redd[tid] += redd[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) {
-    *gnorm = (float)sqrt(redd[0]) * grad_scale;      // ||grad_scale * g||
-    if (step) *step += 1.0f;
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
+// (the optimizer update's two kernels - adam_clip_kernel, grad_norm_kernel - live in st_optim.cuh, shared with st_optim.hip)
 
 // Zero the rows [*valid, cap) of a list of row matrices - the rows a packed bucket layout (st_amd.functional.Rows.bucket
 // with a capacity) leaves to no utterance - in ONE launch per step instead of a whole-matrix memset per buffer (72 of
@@ -1219,8 +1119,8 @@ extern "C" int st_grad_norm(hipStream_t stream, const float* g, long long n, flo
   // them, ce_fwd's 1,200 once 43 us)
   int blocks = (int)((n4 + 1023) / 1024);
   if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(grad_norm_kernel, dim3(blocks), dim3(1024), 0, stream, g, n4, scratch, reinterpret_cast<unsigned*>(scratch + 1024),
-                     gnorm, step, grad_scale);
+  hipLaunchKernelGGL(grad_norm_kernel<false>, dim3(blocks), dim3(1024), 0, stream, g, n4, scratch, reinterpret_cast<unsigned*>(scratch + 1024),
+                     gnorm, step, grad_scale, (float*)nullptr);
   ST_CHECK_LAUNCH();
   return 0;
 }
@@ -1233,8 +1133,8 @@ extern "C" int st_adam_clip(hipStream_t stream, long long n, float* p, float* g,
   const size_t n4 = (size_t)n / 4;
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, lr, step, gnorm, max_norm, beta1,
-                     beta2, eps, grad_scale);
+  hipLaunchKernelGGL((adam_clip_kernel<false, false>), dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, lr, step, gnorm, max_norm, beta1,
+                     beta2, eps, grad_scale, (const float*)nullptr, (float*)nullptr, 0.0f, 0);
   ST_CHECK_LAUNCH();
   return 0;
 }

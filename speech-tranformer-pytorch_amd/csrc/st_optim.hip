@@ -1,0 +1,66 @@
+// The optimizer update with a guard against non-finite gradients and an averaged copy of the weights (gfx950): the forms of
+// st_grad_norm / st_adam_clip that st_optim.cuh builds from the same bodies, and the in-place exchange of two flat buffers that
+// puts the averaged weights under the model.  HBM streams like their neighbours in st_misc.hip: same grids, 16-byte accesses.
+#include "st_optim.cuh"
+
+namespace {
+
+// a <-> b, grid-stride, two 16-byte loads and two 16-byte stores per element
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, size_t n4) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(a + i * 4);
+    const f32x4 y = *reinterpret_cast<const f32x4*>(b + i * 4);
+    *reinterpret_cast<f32x4*>(a + i * 4) = y;
+    *reinterpret_cast<f32x4*>(b + i * 4) = x;
+  }
+}
+
+}  // namespace
+
+extern "C" int st2_grad_norm_guard(hipStream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
+                                   float grad_scale, float* guard) {
+  // scratch: as st_grad_norm (st_grad_norm_blocks() + 1 floats, the ticket zero before the first call); same grid, so the same
+  // partial sums and the same merge order
+  if (n <= 0 || (n & 3) || !g || !scratch || !gnorm || !step || !guard) return -1;
+  const size_t n4 = (size_t)n / 4;
+  int blocks = (int)((n4 + 1023) / 1024);
+  if (blocks > 256) blocks = 256;
+  hipLaunchKernelGGL(grad_norm_kernel<true>, dim3(blocks), dim3(1024), 0, stream, g, n4, scratch,
+                     reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard);
+  ST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int st2_adam_clip_avg(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
+                                 const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
+                                 float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup) {
+  if (n <= 0) return 0;
+  if ((n & 3) || !p || !g || !m || !v || !lr || !step) return -1;
+  if (avg && !(decay >= 0.0f && decay <= 1.0f)) return -1;
+  const size_t n4 = (size_t)n / 4;
+  int blocks = (int)((n4 + 255) / 256);      // st_adam_clip's geometry
+  if (blocks > 4096) blocks = 4096;
+#define ST_ADAM_LAUNCH(GUARD, AVG)                                                                                          \
+  hipLaunchKernelGGL((adam_clip_kernel<GUARD, AVG>), dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, lr, step, gnorm, max_norm, \
+                     beta1, beta2, eps, grad_scale, found_inf, avg, decay, decay_warmup)
+  if (found_inf && avg) ST_ADAM_LAUNCH(true, true);
+  else if (found_inf) ST_ADAM_LAUNCH(true, false);
+  else if (avg) ST_ADAM_LAUNCH(false, true);
+  else ST_ADAM_LAUNCH(false, false);
+#undef ST_ADAM_LAUNCH
+  ST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int st2_swap_f32(hipStream_t stream, float* a, float* b, long long n) {
+  if (n <= 0) return 0;
+  if ((n & 3) || !a || !b || ((size_t)a & 15) || ((size_t)b & 15)) return -1;
+  const float *lo = a < b ? a : b, *hi = a < b ? b : a;
+  if (lo + n > hi) return -1;      // overlapping (or equal) buffers
+  const size_t n4 = (size_t)n / 4;
+  int blocks = (int)((n4 + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(swap_kernel, dim3(blocks), dim3(256), 0, stream, a, b, n4);
+  ST_CHECK_LAUNCH();
+  return 0;
+}

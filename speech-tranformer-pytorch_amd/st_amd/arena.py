@@ -64,6 +64,7 @@ class ParamArena:
         self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
         self.shadow = torch.zeros(total, dtype=torch.bfloat16, device=dev)
+        self.avg = None         # fp32 [total]: the averaged weights, allocated by enable_avg() only
         with torch.no_grad():
             for p in order:
                 v = self.master(p)
@@ -135,6 +136,16 @@ class ParamArena:
     def scope(self):
         """Outermost module forward refreshes the shadow once; nested calls reuse it."""
         return ParamArena._Scope(self)
+
+    # ---- averaged weights ----------------------------------------------------------------------
+    def enable_avg(self) -> torch.Tensor:
+        """Allocate ``avg`` (fp32 [total]) as a copy of ``flat`` as it is now; a second call keeps the buffer."""
+        if self.avg is None:
+            self.avg = self.flat.detach().clone()
+        return self.avg
+
+    def avg_view(self, p, rows=None):
+        return self._view(self.avg, p, rows)
 
     # ---- gradients -----------------------------------------------------------------------------
     def attach_grads(self, params, lo: int, hi: int) -> None:

@@ -1610,6 +1610,62 @@ def adam_clip(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_sca
                                float(grad_scale)), "st_adam_clip")
 
 
+def _scalars(who, *pairs):
+    for t, nm in pairs:
+        if t is not None and not (t.is_cuda and t.dtype == F32 and t.numel() == 1):
+            raise ValueError("%s: %s must be an fp32 scalar on the GPU" % (who, nm))
+
+
+def grad_norm_guard(g, scratch, out, step, guard, grad_scale=1.0):
+    """grad_norm with a verdict (st2_grad_norm_guard): out = grad_scale * ||g||_2; a finite norm advances ``step`` and clears
+    guard[0], a non-finite one leaves ``step`` alone, sets guard[0] = 1 and counts up guard[1].  guard: fp32 [2] on the GPU."""
+    _vec(g, F32, 0, "grad_norm_guard: g")
+    if g.numel() % 4:
+        raise ValueError("grad_norm_guard: g must hold a multiple of 4 elements")
+    _vec(scratch, F32, _norm_blocks() + 1, "scratch")
+    if step is None or guard is None:
+        raise ValueError("grad_norm_guard: step and guard are required")
+    _scalars("grad_norm_guard", (out, "out"), (step, "step"))
+    _dev(guard, F32, (2,), "grad_norm_guard: guard")
+    _tag("grad_norm_guard", g.numel(), io=(4.0 * g.numel(),))
+    _check(load().st2_grad_norm_guard(_stream(), g.data_ptr(), g.numel(), scratch.data_ptr(), out.data_ptr(), step.data_ptr(),
+                                      float(grad_scale), guard.data_ptr()), "st2_grad_norm_guard")
+    return out
+
+
+def adam_clip_avg(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale=1.0, found_inf=None, avg=None,
+                  decay=0.999, decay_warmup=True):
+    """adam_clip plus (st2_adam_clip_avg): found_inf (fp32 device scalar or None) - non-zero: nothing is written; avg (fp32 [n] or
+    None) - avg += w * (p_new - avg), w = 1 - decay, or with decay_warmup 1 - min(decay, (1 + step) / (10 + step))."""
+    n = p.numel()
+    for t, k, nm in ((p, n, "p"), (g, n, "g"), (m, n, "m"), (v, n, "v"), (lr, 1, "lr"), (step, 1, "step"), (gnorm, 1, "gnorm"),
+                     (found_inf, 1, "found_inf"), (avg, n, "avg")):
+        _vec(t, F32, k, nm)
+        if t is not None and t.numel() != k:
+            raise ValueError("adam_clip_avg: %s holds %d elements, expected %d" % (nm, t.numel(), k))
+    if avg is not None and not 0.0 <= float(decay) <= 1.0:
+        raise ValueError("adam_clip_avg: decay must lie in [0, 1], got %r" % (decay,))
+    _tag("adam_clip_avg", n, io=((32.0 if avg is None else 40.0) * n,))      # adam_clip's streams + avg read and written
+    _check(load().st2_adam_clip_avg(_stream(), n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(),
+                                    step.data_ptr(), _p(gnorm), float(max_norm), float(beta1), float(beta2), float(eps),
+                                    float(grad_scale), _p(found_inf), _p(avg), float(decay), int(bool(decay_warmup))),
+           "st2_adam_clip_avg")
+
+
+def swap_(a, b):
+    """Exchange the contents of two fp32 buffers of equal size in place (st2_swap_f32), one launch."""
+    _vec(a, F32, 0, "swap_: a"), _vec(b, F32, a.numel(), "swap_: b")
+    if a.numel() != b.numel() or a.numel() % 4:
+        raise ValueError("swap_: the buffers must hold the same multiple of 4 elements, got %d and %d" % (a.numel(), b.numel()))
+    if a.data_ptr() % 16 or b.data_ptr() % 16:
+        raise ValueError("swap_: the buffers must be 16-byte aligned")
+    lo, hi = sorted((a.data_ptr(), b.data_ptr()))
+    if a.numel() and lo + 4 * a.numel() > hi:
+        raise ValueError("swap_: the buffers overlap")
+    _tag("swap", a.numel(), io=(16.0 * a.numel(),))
+    _check(load().st2_swap_f32(_stream(), a.data_ptr(), b.data_ptr(), a.numel()), "st2_swap_f32")
+
+
 def probe_tr16(inp, out):
     _check(load().st_probe_tr16(_stream(), inp.data_ptr(), out.data_ptr()), "st_probe_tr16")
     return out

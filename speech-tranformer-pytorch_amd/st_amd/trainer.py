@@ -61,7 +61,15 @@ class TrainStep:
         the same projection + loss node and the same captured graph (functional.ce_spec maps the object to the kernels and
         raises ValueError HERE for one the HIP path cannot honour: class weights, another reduction or ignore_index, any
         other module).  ``self.nll`` holds the plain token-mean NLL of the last step as a device scalar - the number that
-        stays comparable across smoothing values (with the plain criterion: the loss itself)."""
+        stays comparable across smoothing values (with the plain criterion: the loss itself).
+
+        The optimizer's options (``ScheduledOptim.enable_nonfinite_guard`` / ``enable_averaging``) need no argument here: the
+        step reads the optimizer.  A captured step holds the launches of the options as they were at capture - after a change
+        the next call raises RuntimeError - and a call inside ``optimizer.averaged()`` raises RuntimeError (the model holds
+        the averaged weights).  A SKIPPED step (non-finite gradient norm under the guard) is still a call: the Noam rate
+        follows the host's ``global_step``, which counts calls, while Adam's bias corrections follow the device step count,
+        which counts applied updates.  Data parallelism needs nothing: the norm is taken after the all-reduce, so every rank
+        reaches the same verdict."""
         self.model, self.optimizer = model, optimizer
         self.vocab_size, self.max_grad_norm = vocab_size, max_grad_norm
         self.crit = criterion or nn.CrossEntropyLoss(ignore_index=0)          # train.py:120
@@ -104,6 +112,14 @@ class TrainStep:
         self._loss = self._gnorm = None
         self._cut = None
         self._seed = None
+
+    def _options(self):
+        """The optimizer's option token (None for an optimizer without options); raises inside ``optimizer.averaged()``."""
+        if getattr(self.optimizer, "_in_averaged", False):
+            raise RuntimeError("%s: called inside optimizer.averaged() - the model holds the averaged weights"
+                               % type(self).__name__)
+        token = getattr(self.optimizer, "options_token", None)
+        return None if token is None else token()
 
     def _backward(self, loss):
         """loss.backward() with a resident gradient seed (autograd's own ones_like(loss) is a fill launch per step)."""
@@ -265,6 +281,7 @@ class TrainStep:
 
     def __call__(self, inputs, input_lengths, targets, target_lengths, ground_truth):
         """inputs [B, T, F] / targets, ground_truth [B, L] on the GPU; lengths on host or GPU."""
+        self._options()
         t_max, l_max = int(input_lengths.max()), int(target_lengths.max())     # host ints when lengths are CPU tensors
         self.global_step += 1
         batch = (inputs[:, :t_max], input_lengths, targets[:, :l_max], target_lengths, ground_truth[:, :l_max])
@@ -367,6 +384,9 @@ class TrainStep:
         return self._replay(st.cap)
 
     def _replay(self, cap):
+        if cap.options != self._options():
+            raise RuntimeError("TrainStep: the optimizer's options changed after this step was captured (the graph holds the "
+                               "old launches): enable the guard / the average before the first capture, or build a new TrainStep")
         self._g_fb, self._g_enc, self._g_opt, self._dec_lo = cap.g_fb, cap.g_enc, cap.g_opt, cap.dec_lo     # (introspection / tests)
         self.nll = cap.nll                                # a static output of the graph, like the loss
         self.optimizer.update_learning_rate(self.global_step)
@@ -399,6 +419,7 @@ class TrainStep:
         if self.reducer is not None and self.reducer.active:
             drain_collective_watchdog()
         cap = _Captured()
+        cap.options = self._options()
         # the captured kernels read the ragged layouts (offsets, lengths, positions, attention work lists, scatter
         # index) by ADDRESS: pin the layout objects of this batch for as long as its graphs live (the layout cache may
         # be flushed by other shapes meanwhile)
@@ -543,10 +564,10 @@ def enable_collective_recorder(entries: int = 512) -> None:
 
 class _Captured:
     """One batch signature's captured step: its graph(s), static result tensors and pinned ragged layouts."""
-    __slots__ = ("g_fb", "g_enc", "g_opt", "loss", "gnorm", "dec_lo", "keep", "nll")
+    __slots__ = ("g_fb", "g_enc", "g_opt", "loss", "gnorm", "dec_lo", "keep", "nll", "options")
 
     def __init__(self):
-        self.g_fb = self.g_enc = self.g_opt = self.loss = self.gnorm = self.keep = self.nll = None
+        self.g_fb = self.g_enc = self.g_opt = self.loss = self.gnorm = self.keep = self.nll = self.options = None
         self.dec_lo = 0
 
 
@@ -582,6 +603,13 @@ class JointTrainStep:
     module) now RAISES ValueError at construction - until this criterion support existed the step silently trained every head
     with the plain cross-entropy.  ``self.nll``: the plain token-mean NLL of the last step's attention branch (a device scalar).
 
+    The optimizer's options (``ScheduledOptim.enable_nonfinite_guard`` / ``enable_averaging``) are read from the optimizer, as
+    in TrainStep, with the JOINT norm as the verdict.  The CTC head lives outside the arena under ``head_optimizer``: with the
+    guard on it must be torch's fused capturable Adam (ValueError otherwise) and gets ``found_inf = optimizer.found_inf`` -
+    it then skips its update and rolls its step count back on that device scalar; with averaging on the head's average is
+    kept here with ``lerp_`` by the device weight ``optimizer.averaging_weight()`` and registered with the optimizer, so
+    ``optimizer.averaged()`` swaps the head's tensors with the arena.
+
     One batch signature at a time (a new signature re-captures)."""
 
     def __init__(self, model: nn.Module, optimizer, head, max_grad_norm: float, head_optimizer=None, use_graph: bool = True,
@@ -598,6 +626,39 @@ class JointTrainStep:
         self.ce_spec = ce_spec(getattr(head, "att_criterion", None), model.tgt_word_proj.weight.shape[0])
         self._ce_denom, self._ce_denom_host = None, None      # as TrainStep: B * l_max (norm "rows") or 1 ("sum") on the device
         self.nll = None
+        self._options_token, self._head_avg = None, None
+        self._bind_options()
+
+    def _bind_options(self):
+        """Carry the optimizer's options over to the head's optimizer (see the class docstring)."""
+        self._options_token = TrainStep._options(self)
+        self._head_avg = None
+        opt, hopt = self.optimizer, self.head_optimizer
+        if hopt is None or self._options_token is None:
+            return
+        if getattr(opt, "found_inf", None) is not None:
+            if not all(g.get("fused") and g.get("capturable") for g in hopt.param_groups):
+                raise ValueError("JointTrainStep: with the non-finite guard on, head_optimizer must be torch's fused capturable "
+                                 "Adam (fused=True, capturable=True): only that one skips its update on a device found_inf")
+            hopt.found_inf = opt.found_inf
+        if getattr(opt, "_avg_opts", None) is not None:
+            params = [q for g in hopt.param_groups for q in g["params"]]
+            self._head_avg = (params, opt.register_averaged(params))
+            self._options_token = TrainStep._options(self)
+
+    def _check_options(self):
+        if TrainStep._options(self) != self._options_token:
+            if self._cap is not None:
+                raise RuntimeError("JointTrainStep: the optimizer's options changed after this step was captured (the graph "
+                                   "holds the old launches): enable them before the first capture, or build a new step")
+            self._bind_options()
+
+    def _average_head(self):
+        if self._head_avg is not None:
+            w = self.optimizer.averaging_weight()          # device scalar, 0 on a skipped step
+            with torch.no_grad():
+                for q, a in zip(*self._head_avg):
+                    a.lerp_(q.detach(), w)
 
     # ---- the parts ------------------------------------------------------------------------------------------------------
     def _part_a1(self, batch, plan, layouts):
@@ -669,6 +730,7 @@ class JointTrainStep:
         gb.mul_(coef)
         self.optimizer.step_captured(grad_norm=gnorm, max_norm=self.max_grad_norm)       # (advances the step count itself)
         self.head_optimizer.step()
+        self._average_head()
         return gnorm
 
     def _joint(self, att, ctc):
@@ -691,6 +753,7 @@ class JointTrainStep:
 
     def __call__(self, inputs, input_lengths, targets, target_lengths, ground_truth):
         """-> (joint loss, attention CE, CTC loss, clip norm): device tensors."""
+        self._check_options()
         t_max, l_max = int(input_lengths.max()), int(target_lengths.max())
         self.global_step += 1
         batch = (inputs[:, :t_max], input_lengths, targets[:, :l_max], target_lengths, ground_truth[:, :l_max])

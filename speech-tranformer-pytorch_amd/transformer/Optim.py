@@ -1,4 +1,6 @@
 """Noam-scheduled Adam (drop-in for reference transformer/Optim.py:6-45)."""
+import contextlib
+
 import torch
 import torch.optim as optim
 
@@ -13,7 +15,16 @@ class ScheduledOptim(object):
     state of ``Adam(model.parameters())``: one ``exp_avg`` / ``exp_avg_sq`` / ``step`` entry per parameter in
     ``model.parameters()`` order, a float learning rate) although the HIP path keeps ONE flat state over the
     parameter arena: the arena offsets give the mapping, so a checkpoint written by the reference (or by this
-    class on the CPU path) resumes here and vice versa (train.py:110-114)."""
+    class on the CPU path) resumes here and vice versa (train.py:110-114).
+
+    Two options of the flat-arena update, both off by default (then the step launches exactly what it launched before they
+    existed), both without a host read:
+      * ``enable_nonfinite_guard()`` (config key ``skip_nonfinite``): a step whose gradient norm is NaN or infinite is SKIPPED -
+        parameters, both moments and Adam's step count keep their bits.  ``found_inf`` (the last step's verdict) and
+        ``skipped`` (the running count) are device scalars: read them when you choose, e.g. once per epoch.
+      * ``enable_averaging(decay, warmup)`` (config keys ``ema_decay``, ``ema_warmup``): an exponential moving average of the
+        weights, kept by the update kernel in the same pass; ``with optimizer.averaged():`` puts it under the model.
+    With either enabled ``state_dict()`` carries one extra top-level key, ``"averaging"``."""
 
     _allow_cpu_arena = False     # tests/_emul.py: exercise the arena path with emulated kernels on the CPU
 
@@ -40,9 +51,108 @@ class ScheduledOptim(object):
             self.optimizer = optim.Adam(params, lr=self.lr, betas=(0.9, 0.98), eps=1e-9)
         self.d_model = d_model
         self.n_warmup_steps = config.n_warmup_steps
+        self._guard = None           # device f32 [2]: (verdict of the last step, number of skipped steps)
+        self._avg_opts = None        # (decay, warmup) once averaging is on; the buffer is arena.avg
+        self._avg_extra = []         # [(tensor, its average)] outside the arena (JointTrainStep: the CTC head)
+        self._in_averaged = False
+        # optional keys: a reference config without them builds exactly the object above
+        if getattr(config, "skip_nonfinite", None):
+            self.enable_nonfinite_guard()
+        if getattr(config, "ema_decay", None) is not None:
+            warm = getattr(config, "ema_warmup", None)
+            self.enable_averaging(decay=config.ema_decay, warmup=True if warm is None else bool(warm))
+
+    # ---- options of the flat-arena update ----------------------------------------------------------------
+    def _plain(self):
+        group = self.optimizer.param_groups[0]
+        return not (group["weight_decay"] or group["amsgrad"] or group["maximize"])
+
+    def _require_hip_update(self, what):
+        if self.arena is None:
+            raise ValueError("ScheduledOptim.%s: needs the flat-arena path (the model on the GPU)" % what)
+        if not self._plain():
+            raise ValueError("ScheduledOptim.%s: weight decay / amsgrad / maximize take torch's own Adam, which has neither "
+                             "the guard nor the average" % what)
+
+    def enable_nonfinite_guard(self):
+        """Skip every update whose gradient norm is not finite (see the class docstring).  Before the first capture."""
+        self._require_hip_update("enable_nonfinite_guard")
+        if self._guard is None:
+            self._guard = torch.zeros(2, dtype=torch.float32, device=self.arena.device)
+
+    def enable_averaging(self, decay=0.999, warmup=True):
+        """Keep avg += (1 - d) * (p - avg) after every applied update; d = decay, or with warmup min(decay, (1 + t) / (10 + t))
+        at Adam step count t.  The average starts as a copy of the parameters as they are now.  Before the first capture."""
+        self._require_hip_update("enable_averaging")
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError("ScheduledOptim.enable_averaging: decay must lie in [0, 1], got %r" % (decay,))
+        self.arena.enable_avg()
+        self._avg_opts = (float(decay), bool(warmup))
+
+    @property
+    def found_inf(self):
+        """Device scalar: 1 when the last step was skipped for a non-finite gradient norm, else 0 (None: guard off)."""
+        return None if self._guard is None else self._guard[0]
+
+    @property
+    def skipped(self):
+        """Device scalar: how many steps the guard has skipped so far (None: guard off)."""
+        return None if self._guard is None else self._guard[1]
+
+    def options_token(self):
+        """What a captured step depends on: TrainStep records it at capture and refuses to replay after a change."""
+        return (self._guard is not None, self._avg_opts, len(self._avg_extra))
+
+    def averaging_weight(self):
+        """Device scalar w of this step's average update, 0 on a skipped step - for tensors outside the arena, whose
+        average JointTrainStep keeps with torch ops (call AFTER step_captured: the step count is already advanced)."""
+        decay, warmup = self._avg_opts
+        t = self._flat_state()[1]["step"]
+        d = torch.clamp((1.0 + t) / (10.0 + t), max=decay) if warmup else torch.full_like(t, decay)
+        w = 1.0 - d
+        return w if self._guard is None else w * (1.0 - self._guard[0])
+
+    def register_averaged(self, tensors):
+        """Tensors outside the arena whose average the caller keeps (their averages start as copies): averaged() swaps
+        them with the arena.  -> the list of average tensors, in order."""
+        if self._avg_opts is None:
+            raise ValueError("ScheduledOptim.register_averaged: averaging is not enabled")
+        self._avg_extra = [(t, t.detach().clone()) for t in tensors]
+        return [a for _, a in self._avg_extra]
+
+    def _swap_averaged(self):
+        from st_amd import native as nv
+        nv.swap_(self.arena.flat, self.arena.avg)
+        with torch.no_grad():
+            for t, a in self._avg_extra:
+                tmp = t.detach().clone()
+                t.copy_(a)
+                a.copy_(tmp)
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside the context the model holds the averaged weights (one launch swaps ``arena.flat`` and ``arena.avg`` in
+        place - parameter views and captured graphs hold addresses into the arena, so the pointers cannot be exchanged);
+        the exit swaps back.  The bf16 shadow and the weight-fragment layouts are rebuilt by every outermost forward
+        (``arena.scope()``), so eval forwards and Decode see the weights that are in ``flat`` at that moment.  No update may
+        run inside; nesting raises."""
+        if self._avg_opts is None:
+            raise RuntimeError("ScheduledOptim.averaged: averaging is not enabled")
+        if self._in_averaged:
+            raise RuntimeError("ScheduledOptim.averaged: already inside averaged()")
+        self._swap_averaged()
+        self._in_averaged = True
+        try:
+            yield self
+        finally:
+            self._in_averaged = False
+            self._swap_averaged()
 
     def step(self, global_step):
         self.update_learning_rate(global_step)
+        if self._guard is not None or self._avg_opts is not None:
+            self.step_captured(grad_norm=True, max_norm=float("inf"))      # (the HIP update; an infinite bound clips nothing)
+            return
         self.optimizer.step()
 
     def _flat_state(self):
@@ -69,9 +179,20 @@ class ScheduledOptim(object):
         ``st_adam_clip`` (clip + the arithmetic of torch's fused Adam, on this optimizer's own state tensors).
         grad_norm: True = compute it here (returned as a device scalar), or a device scalar already computed.
         grad_scale: the gradient buffer still has to be multiplied by this (st_amd.dp.GradReducer.synchronize(divide=False)
-        leaves the rank SUM and returns 1 / world): folded into the norm and the clip coefficient - no pass of its own."""
+        leaves the rank SUM and returns 1 / world): folded into the norm and the clip coefficient - no pass of its own.
+        With the guard or the average enabled the two launches are ``st2_grad_norm_guard`` and ``st2_adam_clip_avg``; a norm
+        handed in (the joint step) gives the verdict through torch ops on that scalar - no host read either way."""
         group = self.optimizer.param_groups[0]
         plain = not (group["weight_decay"] or group["amsgrad"] or group["maximize"])
+        guard, averaging = self._guard is not None, self._avg_opts is not None
+        if guard or averaging:
+            if self._in_averaged:
+                raise RuntimeError("ScheduledOptim.step_captured: inside averaged() the model holds the averaged weights")
+            if guard and grad_norm is None:
+                raise ValueError("ScheduledOptim.step_captured: the non-finite guard needs a norm (grad_norm=True or a scalar)")
+            if grad_norm is None or max_norm is None or not plain:
+                raise ValueError("ScheduledOptim.step_captured: the guard / the average exist in the HIP update only "
+                                 "(grad_norm and max_norm given, no weight decay / amsgrad / maximize)")
         if self.arena is None or grad_norm is None:
             if grad_scale != 1.0:
                 for q in self.optimizer.param_groups[0]["params"]:
@@ -95,13 +216,27 @@ class ScheduledOptim(object):
         p, st = self._flat_state()
         if grad_norm is True:
             self.norm_scratch(p.device)
-            grad_norm = nv.grad_norm(p.grad, self._norm_scratch, torch.empty((), dtype=torch.float32, device=p.device), step=st["step"],
-                                     grad_scale=grad_scale)
+            out = torch.empty((), dtype=torch.float32, device=p.device)
+            if guard:
+                grad_norm = nv.grad_norm_guard(p.grad, self._norm_scratch, out, st["step"], self._guard, grad_scale=grad_scale)
+            else:
+                grad_norm = nv.grad_norm(p.grad, self._norm_scratch, out, step=st["step"], grad_scale=grad_scale)
+        elif guard:
+            found = (~torch.isfinite(grad_norm)).to(torch.float32).reshape(())
+            self._guard[0].copy_(found)
+            self._guard[1].add_(found)
+            st["step"].add_(1.0 - found)
         else:
             st["step"].add_(1)
         beta1, beta2 = group["betas"]
-        nv.adam_clip(p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], self.lr_tensor, st["step"], grad_norm, max_norm,
-                     beta1, beta2, group["eps"], grad_scale=grad_scale)
+        if guard or averaging:
+            decay, warmup = self._avg_opts if averaging else (1.0, False)
+            nv.adam_clip_avg(p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], self.lr_tensor, st["step"], grad_norm, max_norm,
+                             beta1, beta2, group["eps"], grad_scale=grad_scale, found_inf=self.found_inf,
+                             avg=self.arena.avg if averaging else None, decay=decay, decay_warmup=warmup)
+        else:
+            nv.adam_clip(p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], self.lr_tensor, st["step"], grad_norm, max_norm,
+                         beta1, beta2, group["eps"], grad_scale=grad_scale)
         return grad_norm
 
     def zero_grad(self):
@@ -128,7 +263,16 @@ class ScheduledOptim(object):
         # the hyper-parameters a plain ``optim.Adam(model.parameters(), ...)`` saves (Optim.py:11-16)
         g = {k: v for k, v in group.items() if k != "params"}
         g.update(lr=float(self.lr), fused=None, capturable=False, foreach=None, params=list(range(len(self._params))))
-        return {"state": state, "param_groups": [g]}
+        out = {"state": state, "param_groups": [g]}
+        if self._guard is not None or self._avg_opts is not None:
+            # the one key beyond the reference's format; absent when nothing is enabled
+            extra = {"skipped": 0.0 if self._guard is None else float(self._guard[1])}
+            if self._avg_opts is not None:
+                extra.update(decay=self._avg_opts[0], warmup=self._avg_opts[1],
+                             avg=[self.arena.avg_view(p).detach().clone() for p in self._params],
+                             extra=[a.detach().clone() for _, a in self._avg_extra])
+            out["averaging"] = extra
+        return out
 
     def load_state_dict(self, optimizer_state_dict):
         if self.arena is None:
@@ -173,6 +317,29 @@ class ScheduledOptim(object):
         self.lr_tensor.fill_(self.lr)
         for g in self.optimizer.param_groups:
             g["lr"] = self.lr_tensor
+        self._load_averaging(optimizer_state_dict.get("averaging"))
+
+    def _load_averaging(self, extra):
+        """The "averaging" key of a checkpoint into whatever is enabled HERE (decay / warmup stay as enabled); a checkpoint
+        without the key - or without averages - re-seeds the average from the parameters."""
+        extra = extra or {}
+        if self._guard is not None:
+            self._guard.zero_()
+            self._guard[1].fill_(float(extra.get("skipped", 0.0)))
+        if self._avg_opts is None:
+            return
+        saved = extra.get("avg")
+        with torch.no_grad():
+            if saved is None:
+                self.arena.avg.copy_(self.arena.flat)
+            else:
+                if len(saved) != len(self._params) or any(a.numel() != p.numel() for a, p in zip(saved, self._params)):
+                    raise ValueError("ScheduledOptim.load_state_dict: the checkpoint's averaged tensors do not match the model")
+                for a, p in zip(saved, self._params):
+                    self.arena.avg_view(p).copy_(a.reshape(p.shape))
+            more = extra.get("extra") or []
+            for i, (t, a) in enumerate(self._avg_extra):
+                a.copy_(more[i] if len(more) == len(self._avg_extra) else t)
 
     def update_learning_rate(self, global_step):
         self.lr = learn_rate(self.d_model, self.n_warmup_steps, global_step)
