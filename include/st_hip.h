@@ -641,7 +641,7 @@ int stx_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, i
  * T_raw = (len[b] - 1) * interval + 1 + right (0 when len[b] < 1) with len on the DEVICE: pass (interval 1, right 0) with raw
  * lengths, or the stacking geometry with the lengths of already stacked / subsampled rows - then T_raw is the last raw frame
  * that can appear in a row, plus one.  n_time + n_freq <= 64. */
-#define ST2_VERSION 2
+#define ST2_VERSION 3
 int st2_version(void);
 int st2_specaug_plan(st_stream_t stream, const unsigned* seed, unsigned salt, const int* len, int B, int interval, int right,
                      int n_time, int time_width, int time_ratio_permille, int n_freq, int freq_width, int mel_bins, int* table);
@@ -681,6 +681,35 @@ int st2_adam_clip_avg(st_stream_t stream, long long n, float* p, float* g, float
 /* Exchange two fp32 buffers in place (n % 4 == 0, both 16-byte aligned, not overlapping): the averaged weights go under the
  * model and back.  A pointer swap is not possible - parameter views and captured graphs hold addresses into the arena. */
 int st2_swap_f32(st_stream_t stream, float* a, float* b, long long n);
+
+/* ---- st2_, version 3: gradient accumulation over micro-batches with an on-device denominator --------------------------------
+ * A WINDOW of micro-batches adds the gradients of their SUM losses into the flat gradient buffer; what the window divides by
+ * (its token count, say) is known only after the last one, and never on the host.  win (device f32 [4]) is the window's state:
+ * [0] the denominator, [1] the sum of row losses, [2] the sum of plain NLL, [3] micro-batches noted.  Counts stay exact in
+ * fp32 up to 2^24.
+ *
+ * st2_accum_note: one micro-batch joins the window, after its loss forward (one thread).  sums: the f32 [4] that
+ * stx_ce_smooth_fwd left (run with a denominator of 1.0).  win[1] += sums[0]; win[2] += sums[3] * sums[1] (nothing when
+ * sums[1] == 0: the NLL mean of no token is 0 / 0, their sum is 0); win[3] += 1; win[0] += *d - or, d NULL, win[0] = 1 (a SUM
+ * criterion: no division).  out[0] = the micro-batch's own loss, sums[0] / *d (d NULL: sums[0]).  d may point into sums. */
+int st2_accum_note(st_stream_t stream, const float* sums, const float* d, float* win, float* out);
+/* st2_grad_norm_guard over a window: *gnorm = grad_scale * ||g|| / win[0].  guard may be NULL (no verdict: *step += 1 always);
+ * with a guard the verdict is ALSO bad when win[0] <= 0 (a window without a single token: nothing to divide by).  Partial sums
+ * and the fixed-order fp64 merge are unchanged: with win[0] == 1 and finite input *gnorm equals st2_grad_norm_guard's bit for
+ * bit (a division by 1.0f is exact). */
+int st2_grad_norm_win(st_stream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
+                      float grad_scale, float* guard, const float* win);
+/* st2_adam_clip_avg over a window.  The coefficient every gradient element is multiplied by is
+ * min(1, max_norm / (*gnorm + 1e-6)) * grad_scale / win[0], one fp32 scalar formed before the loop; *gnorm is
+ * st2_grad_norm_win's.  g is left holding ZEROS, not the clipped gradient: the update is the next window's zero_grad.  Under
+ * *found_inf != 0 the zeros are the only thing written - p, m, v and avg keep their bits.  With win[0] == 1 and found_inf clear
+ * p, m, v and avg equal st2_adam_clip_avg's bit for bit. */
+int st2_adam_clip_win(st_stream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
+                      const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
+                      float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup, const float* win);
+/* The window's results, then a fresh window (one thread; after the update in stream order): out f32 [4] = {win[1] / win[0],
+ * win[2] / win[0], win[0], win[3]} = {loss, plain NLL, denominator, micro-batches}; win = 0. */
+int st2_window_close(st_stream_t stream, float* win, float* out);
 
 #ifdef __cplusplus
 }

@@ -1120,7 +1120,7 @@ extern "C" int st_grad_norm(hipStream_t stream, const float* g, long long n, flo
   int blocks = (int)((n4 + 1023) / 1024);
   if (blocks > 256) blocks = 256;
   hipLaunchKernelGGL(grad_norm_kernel<false>, dim3(blocks), dim3(1024), 0, stream, g, n4, scratch, reinterpret_cast<unsigned*>(scratch + 1024),
-                     gnorm, step, grad_scale, (float*)nullptr);
+                     gnorm, step, grad_scale, (float*)nullptr, (const float*)nullptr);
   ST_CHECK_LAUNCH();
   return 0;
 }
@@ -1134,7 +1134,7 @@ extern "C" int st_adam_clip(hipStream_t stream, long long n, float* p, float* g,
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL((adam_clip_kernel<false, false>), dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, lr, step, gnorm, max_norm, beta1,
-                     beta2, eps, grad_scale, (const float*)nullptr, (float*)nullptr, 0.0f, 0);
+                     beta2, eps, grad_scale, (const float*)nullptr, (float*)nullptr, 0.0f, 0, (const float*)nullptr);
   ST_CHECK_LAUNCH();
   return 0;
 }

@@ -2,6 +2,9 @@
 // serves both cross-entropy kernels): st_misc.hip instantiates the plain forms (st_grad_norm, st_adam_clip), st_optim.hip the
 // forms with a non-finite verdict and an averaged copy of the weights (st2_grad_norm_guard, st2_adam_clip_avg).  The template
 // switches only ADD statements: with both off the arithmetic, its order and the stores are those of the plain kernels.
+// A third switch, WIN, serves gradient accumulation over micro-batches (st2_grad_norm_win, st2_adam_clip_win): the gradient
+// buffer holds a SUM whose denominator win[0] is a device scalar known only after the last micro-batch; dividing by 1.0f is
+// exact, so at win[0] == 1 the WIN forms compute what the forms without it compute, bit for bit.
 #pragma once
 #include "st_common.cuh"
 
@@ -19,18 +22,29 @@ namespace {
 // st2_adam_clip_avg: GUARD - a non-zero *found_inf makes the whole launch a no-op, nothing is written; AVG - the exponential
 // moving average of the parameters, avg += w * (p_new - avg) in the same pass, w = 1 - d, d = decay or (decay_warmup)
 // min(decay, (1 + step) / (10 + step)).  Two switches, so that the guard alone streams exactly what the plain kernel streams.
-template <bool GUARD, bool AVG>
+// st2_adam_clip_win: WIN - the coefficient is also divided by win[0] (still ONE scalar, formed before the loop), and ZEROS are
+// stored to g where the clipped gradient would go: the update is the next window's zero_grad at no extra traffic.  Under WIN a
+// non-zero *found_inf still clears g (the skipped window's sum must not leak into the next one) and writes nothing else.
+template <bool GUARD, bool AVG, bool WIN = false>
 __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, size_t n4, const float* lr_p,
                                                         const float* step_p, const float* gnorm_p, float max_norm,
                                                         float beta1, float beta2, float eps, float grad_scale,
                                                         const float* found_inf, float* __restrict__ avg, float decay,
-                                                        int decay_warmup) {
-  if (GUARD && *found_inf != 0.0f) return;      // (uniform over the grid: every workgroup reads the same scalar)
+                                                        int decay_warmup, const float* win) {
+  if (GUARD && *found_inf != 0.0f) {      // (uniform over the grid: every workgroup reads the same scalar)
+    if (WIN) {
+      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+      for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x)
+        store16<ST_ADAM_SC1>(g + i * 4, zero);
+    }
+    return;
+  }
   const float lr = *lr_p, step = *step_p;
   // grad_scale: what the buffer still has to be multiplied by to be THE gradient (1 / world behind a summing all-reduce:
   // the rank average costs no pass of its own); *gnorm_p is the norm of the scaled gradient (st_grad_norm's grad_scale)
-  const float coef = (gnorm_p ? fminf(max_norm / (*gnorm_p + 1e-6f), 1.0f) : 1.0f) * grad_scale;
+  float coef = (gnorm_p ? fminf(max_norm / (*gnorm_p + 1e-6f), 1.0f) : 1.0f) * grad_scale;
+  if (WIN) coef = coef / *win;      // the window's denominator; *gnorm_p is the norm of the DIVIDED gradient (st2_grad_norm_win)
   const float bc1 = 1.0f - powf(beta1, step), bc2 = 1.0f - powf(beta2, step);
   const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2);
   float w = 0.0f;
@@ -46,7 +60,7 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, f
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float ge = gg[e] * coef;
-      gg[e] = ge;
+      gg[e] = WIN ? 0.0f : ge;
       mm[e] = mm[e] + (1.0f - beta1) * (ge - mm[e]);          // lerp(m, g, 1 - beta1), as torch
       vv[e] = beta2 * vv[e] + (1.0f - beta2) * ge * ge;
       const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
@@ -71,9 +85,11 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, f
 // plus a memset) and the separate step increment: three graph nodes -> one.
 // GUARD (st2_grad_norm_guard): the same single writer also leaves the verdict - a non-finite norm does not advance the step,
 // sets guard[0] and counts up guard[1]; a finite one clears guard[0].
-template <bool GUARD>
+// WIN (st2_grad_norm_win): the norm is divided by the window's denominator win[0], and a denominator <= 0 is a bad verdict too.
+template <bool GUARD, bool WIN = false>
 __global__ __launch_bounds__(1024) void grad_norm_kernel(const float* __restrict__ g, size_t n4, float* partial, unsigned* ticket,
-                                                        float* __restrict__ gnorm, float* step, float grad_scale, float* guard) {
+                                                        float* __restrict__ gnorm, float* step, float grad_scale, float* guard,
+                                                        const float* win) {
   __shared__ float red[16];      // 1024 threads x four 16-byte loads in flight = 64 KB per workgroup, 16 MB over the chip
                                  // (256 threads: 4 MB in flight = ~2 TB/s at ~2 us memory latency: 18 us for 52 MB)
   __shared__ bool last;
@@ -125,11 +141,12 @@ __global__ __launch_bounds__(1024) void grad_norm_kernel(const float* __restrict
     __syncthreads();
   }
   if (tid == 0) {
-    const float norm = (float)sqrt(redd[0]) * grad_scale;      // ||grad_scale * g||
+    float norm = (float)sqrt(redd[0]) * grad_scale;      // ||grad_scale * g||
+    if (WIN) norm = norm / *win;
     *gnorm = norm;
     if (GUARD) {
       // NaN and +-inf elements, and a workgroup's fp32 sum of squares that overflowed, all arrive here as a NaN or inf norm
-      const bool bad = !(fabsf(norm) <= 3.402823466e38f);
+      const bool bad = !(fabsf(norm) <= 3.402823466e38f) || (WIN && !(*win > 0.0f));
       if (!bad) *step += 1.0f;
       guard[0] = bad ? 1.0f : 0.0f;
       if (bad) guard[1] += 1.0f;

@@ -1,6 +1,8 @@
 // The optimizer update with a guard against non-finite gradients and an averaged copy of the weights (gfx950): the forms of
 // st_grad_norm / st_adam_clip that st_optim.cuh builds from the same bodies, and the in-place exchange of two flat buffers that
 // puts the averaged weights under the model.  HBM streams like their neighbours in st_misc.hip: same grids, 16-byte accesses.
+// Gradient accumulation over micro-batches adds the WIN forms of the two kernels and the two one-thread launches that keep the
+// window's state (denominator, loss sums, count) in device memory: st2_accum_note, st2_window_close.
 #include "st_optim.cuh"
 
 namespace {
@@ -15,6 +17,36 @@ __global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float*
   }
 }
 
+// One micro-batch noted in the window (see st2_accum_note in include/st_hip.h); one thread, plain stores.
+__global__ void accum_note_kernel(const float* __restrict__ sums, const float* d, float* __restrict__ win, float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float s = sums[0], n = sums[1];
+  win[1] += s;
+  if (n > 0.0f) win[2] += sums[3] * n;      // (no token: sums[3] is 0 / 0, and the sum of no NLL is 0)
+  win[3] += 1.0f;
+  if (d) {
+    const float dd = *d;
+    win[0] += dd;
+    out[0] = s / dd;
+  } else {
+    win[0] = 1.0f;
+    out[0] = s;
+  }
+}
+
+__global__ void window_close_kernel(float* __restrict__ win, float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float d = win[0];
+  out[0] = win[1] / d;
+  out[1] = win[2] / d;
+  out[2] = d;
+  out[3] = win[3];
+  win[0] = 0.0f;
+  win[1] = 0.0f;
+  win[2] = 0.0f;
+  win[3] = 0.0f;
+}
+
 }  // namespace
 
 extern "C" int st2_grad_norm_guard(hipStream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
@@ -26,28 +58,87 @@ extern "C" int st2_grad_norm_guard(hipStream_t stream, const float* g, long long
   int blocks = (int)((n4 + 1023) / 1024);
   if (blocks > 256) blocks = 256;
   hipLaunchKernelGGL(grad_norm_kernel<true>, dim3(blocks), dim3(1024), 0, stream, g, n4, scratch,
-                     reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard);
+                     reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard, (const float*)nullptr);
   ST_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int st2_adam_clip_avg(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
-                                 const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
-                                 float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup) {
+extern "C" int st2_grad_norm_win(hipStream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
+                                 float grad_scale, float* guard, const float* win) {
+  // st2_grad_norm_guard's geometry: same partial sums, same merge order; guard NULL = no verdict (step always advances)
+  if (n <= 0 || (n & 3) || !g || !scratch || !gnorm || !step || !win) return -1;
+  const size_t n4 = (size_t)n / 4;
+  int blocks = (int)((n4 + 1023) / 1024);
+  if (blocks > 256) blocks = 256;
+  if (guard)
+    hipLaunchKernelGGL((grad_norm_kernel<true, true>), dim3(blocks), dim3(1024), 0, stream, g, n4, scratch,
+                       reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard, win);
+  else
+    hipLaunchKernelGGL((grad_norm_kernel<false, true>), dim3(blocks), dim3(1024), 0, stream, g, n4, scratch,
+                       reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard, win);
+  ST_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
+
+// the shared launcher of st2_adam_clip_avg (win NULL) and st2_adam_clip_win
+int adam_clip_launch(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr, const float* step,
+                     const float* gnorm, float max_norm, float beta1, float beta2, float eps, float grad_scale,
+                     const float* found_inf, float* avg, float decay, int decay_warmup, const float* win) {
   if (n <= 0) return 0;
   if ((n & 3) || !p || !g || !m || !v || !lr || !step) return -1;
   if (avg && !(decay >= 0.0f && decay <= 1.0f)) return -1;
   const size_t n4 = (size_t)n / 4;
   int blocks = (int)((n4 + 255) / 256);      // st_adam_clip's geometry
   if (blocks > 4096) blocks = 4096;
-#define ST_ADAM_LAUNCH(GUARD, AVG)                                                                                          \
-  hipLaunchKernelGGL((adam_clip_kernel<GUARD, AVG>), dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, lr, step, gnorm, max_norm, \
-                     beta1, beta2, eps, grad_scale, found_inf, avg, decay, decay_warmup)
-  if (found_inf && avg) ST_ADAM_LAUNCH(true, true);
-  else if (found_inf) ST_ADAM_LAUNCH(true, false);
-  else if (avg) ST_ADAM_LAUNCH(false, true);
-  else ST_ADAM_LAUNCH(false, false);
+#define ST_ADAM_LAUNCH(GUARD, AVG, WIN)                                                                                      \
+  hipLaunchKernelGGL((adam_clip_kernel<GUARD, AVG, WIN>), dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, lr, step, gnorm, \
+                     max_norm, beta1, beta2, eps, grad_scale, found_inf, avg, decay, decay_warmup, win)
+  if (win) {
+    if (found_inf && avg) ST_ADAM_LAUNCH(true, true, true);
+    else if (found_inf) ST_ADAM_LAUNCH(true, false, true);
+    else if (avg) ST_ADAM_LAUNCH(false, true, true);
+    else ST_ADAM_LAUNCH(false, false, true);
+  } else {
+    if (found_inf && avg) ST_ADAM_LAUNCH(true, true, false);
+    else if (found_inf) ST_ADAM_LAUNCH(true, false, false);
+    else if (avg) ST_ADAM_LAUNCH(false, true, false);
+    else ST_ADAM_LAUNCH(false, false, false);
+  }
 #undef ST_ADAM_LAUNCH
+  ST_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int st2_adam_clip_avg(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
+                                 const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
+                                 float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup) {
+  return adam_clip_launch(stream, n, p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale, found_inf, avg, decay,
+                          decay_warmup, nullptr);
+}
+
+extern "C" int st2_adam_clip_win(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
+                                 const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
+                                 float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup,
+                                 const float* win) {
+  if (!win) return -1;
+  return adam_clip_launch(stream, n, p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale, found_inf, avg, decay,
+                          decay_warmup, win);
+}
+
+extern "C" int st2_accum_note(hipStream_t stream, const float* sums, const float* d, float* win, float* out) {
+  if (!sums || !win || !out) return -1;
+  hipLaunchKernelGGL(accum_note_kernel, dim3(1), dim3(64), 0, stream, sums, d, win, out);
+  ST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int st2_window_close(hipStream_t stream, float* win, float* out) {
+  if (!win || !out) return -1;
+  hipLaunchKernelGGL(window_close_kernel, dim3(1), dim3(64), 0, stream, win, out);
   ST_CHECK_LAUNCH();
   return 0;
 }

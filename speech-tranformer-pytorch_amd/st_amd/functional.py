@@ -1303,6 +1303,7 @@ class VocabCeFn(torch.autograd.Function):
         ctx.save_for_backward(x, logits, target, lse, sums, index, denom)
         ctx.mod, ctx.ignore_index, ctx.spec, ctx.V = mod, ignore_index, spec, V
         mod._st_ce_nll = sums[2] if spec is None else sums[3]
+        mod._st_ce_sums = sums              # (the kernel's whole result: an accumulating TrainStep notes it in its window)
         return sums[2]
 
     @staticmethod

@@ -80,7 +80,7 @@ def _read_header() -> str:
 SIGNATURES, ABI_VERSION, _EPI = parse_header(_read_header())
 # ... and the same for the header's extension section (the stx_* entry points)
 EXT_SIGNATURES, EXT_VERSION = parse_extension(_read_header())
-# ... and its second extension section (st2_*: SpecAugment)
+# ... and its second extension section (st2_*: SpecAugment, the optimizer's options, gradient accumulation)
 EXT2_SIGNATURES, EXT2_VERSION = parse_extension(_read_header(), "st2")
 (EPI_BF16, EPI_BF16_RELU, EPI_F32, EPI_BF16_MASK, EPI_BF16_ADD, EPI_F32_ATOMIC, EPI_F32_ATOMIC_T, EPI_BF16_DELTA) = (
     _EPI["ST_" + k] for k in ("EPI_BF16", "EPI_BF16_RELU", "EPI_F32", "EPI_BF16_MASK", "EPI_BF16_ADD", "EPI_F32_ATOMIC",
@@ -1664,6 +1664,76 @@ def swap_(a, b):
         raise ValueError("swap_: the buffers overlap")
     _tag("swap", a.numel(), io=(16.0 * a.numel(),))
     _check(load().st2_swap_f32(_stream(), a.data_ptr(), b.data_ptr(), a.numel()), "st2_swap_f32")
+
+
+# ---- gradient accumulation over micro-batches: the window's state in device memory (st2_, version 3) -------------------------
+def accum_note(sums, d, win, out):
+    """One micro-batch joins the window (st2_accum_note): win[1] += sums[0], win[2] += sums[3] * sums[1], win[3] += 1,
+    win[0] += d (d None: win[0] = 1); out[0] = sums[0] / d, the micro-batch's own loss.  sums: the fp32 [4] of ce_smooth_fwd run
+    with a denominator of 1; d: a 1-element fp32 device tensor (a view into sums is fine) or None; win: fp32 [4]."""
+    _dev(sums, F32, (4,), "accum_note: sums"), _dev(win, F32, (4,), "accum_note: win")
+    _scalars("accum_note", (d, "d"), (out, "out"))
+    if out is None:
+        raise ValueError("accum_note: out is required")
+    if d is not None and not d.is_contiguous():
+        raise ValueError("accum_note: d must be contiguous")
+    _tag("accum_note", 1)
+    _check(load().st2_accum_note(_stream(), sums.data_ptr(), _p(d), win.data_ptr(), out.data_ptr()), "st2_accum_note")
+    return out
+
+
+def window_close(win, out):
+    """out (fp32 [4]) = (win[1] / win[0], win[2] / win[0], win[0], win[3]): the window's loss, plain NLL, denominator and
+    micro-batch count; then win = 0 (st2_window_close)."""
+    _dev(win, F32, (4,), "window_close: win"), _dev(out, F32, (4,), "window_close: out")
+    if win.data_ptr() == out.data_ptr():
+        raise ValueError("window_close: win and out must be different buffers")
+    _tag("window_close", 1)
+    _check(load().st2_window_close(_stream(), win.data_ptr(), out.data_ptr()), "st2_window_close")
+    return out
+
+
+def grad_norm_win(g, scratch, out, step, guard, win, grad_scale=1.0):
+    """grad_norm_guard over a window (st2_grad_norm_win): out = grad_scale * ||g||_2 / win[0]; guard (fp32 [2]) may be None -
+    then ``step`` always advances; with a guard a denominator win[0] <= 0 is a bad verdict as well."""
+    if step is None or win is None:
+        raise ValueError("grad_norm_win: step and win are required")
+    _vec(g, F32, 0, "grad_norm_win: g")
+    if g.numel() == 0 or g.numel() % 4:
+        raise ValueError("grad_norm_win: g must hold a positive multiple of 4 elements")
+    _vec(scratch, F32, _norm_blocks() + 1, "scratch")
+    _scalars("grad_norm_win", (out, "out"), (step, "step"))
+    if guard is not None:
+        _dev(guard, F32, (2,), "grad_norm_win: guard")
+    _dev(win, F32, (4,), "grad_norm_win: win")
+    _tag("grad_norm_win", g.numel(), io=(4.0 * g.numel(),))
+    _check(load().st2_grad_norm_win(_stream(), g.data_ptr(), g.numel(), scratch.data_ptr(), out.data_ptr(), step.data_ptr(),
+                                    float(grad_scale), _p(guard), win.data_ptr()), "st2_grad_norm_win")
+    return out
+
+
+def adam_clip_win(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, win, grad_scale=1.0, found_inf=None, avg=None,
+                  decay=0.999, decay_warmup=True):
+    """adam_clip_avg over a window (st2_adam_clip_win): the gradient is also divided by win[0] (win: fp32 [4]) and g is left
+    holding ZEROS; under a non-zero found_inf the zeros are all that is written."""
+    if win is None:
+        raise ValueError("adam_clip_win: win is required")
+    n = p.numel()
+    for t, k, nm in ((p, n, "p"), (g, n, "g"), (m, n, "m"), (v, n, "v"), (lr, 1, "lr"), (step, 1, "step"), (gnorm, 1, "gnorm"),
+                     (found_inf, 1, "found_inf"), (avg, n, "avg")):
+        _vec(t, F32, k, nm)
+        if t is not None and t.numel() != k:
+            raise ValueError("adam_clip_win: %s holds %d elements, expected %d" % (nm, t.numel(), k))
+    _dev(win, F32, (4,), "adam_clip_win: win")
+    if n % 4:
+        raise ValueError("adam_clip_win: the buffers must hold a multiple of 4 elements")
+    if avg is not None and not 0.0 <= float(decay) <= 1.0:
+        raise ValueError("adam_clip_win: decay must lie in [0, 1], got %r" % (decay,))
+    _tag("adam_clip_win", n, io=((32.0 if avg is None else 40.0) * n,))
+    _check(load().st2_adam_clip_win(_stream(), n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(),
+                                    step.data_ptr(), _p(gnorm), float(max_norm), float(beta1), float(beta2), float(eps),
+                                    float(grad_scale), _p(found_inf), _p(avg), float(decay), int(bool(decay_warmup)),
+                                    win.data_ptr()), "st2_adam_clip_win")
 
 
 def probe_tr16(inp, out):

@@ -24,6 +24,12 @@ backward - ~40 % of the step - is executing.  The bucket all-reduces are capture
 step graph (``dp_in_graph``; RCCL collectives are stream-capturable), so a DP step is one graph
 replay; where that capture is refused the three parts become three graphs with eager
 collectives between them.
+
+Gradient accumulation (``TrainStep(..., accumulate=K)``): K calls are K micro-batches of ONE update whose objective is what one
+step on their concatenation would compute.  Every micro-batch adds the gradient of its SUM loss into the flat buffer; the
+denominator (the window's token count, say) is summed on the device and applied once, inside the norm and the clip + Adam
+kernels of the update (st2_grad_norm_win, st2_adam_clip_win) - no host read, and the update kernel leaves the buffer zeroed for
+the next window.  In graph mode the micro-batch and the update are two captures.
 """
 from __future__ import annotations
 
@@ -40,7 +46,7 @@ from .arena import arena_of
 from .dp import GradReducer
 from . import rng
 from . import native as nv
-from .functional import TailBuffers, ce_spec, deferred_wgrads
+from .functional import CeSpec, TailBuffers, ce_spec, deferred_wgrads
 
 
 def clip_grad_norm_flat(arena, max_norm: float) -> torch.Tensor:
@@ -55,7 +61,8 @@ def clip_grad_norm_flat(arena, max_norm: float) -> torch.Tensor:
 class TrainStep:
     def __init__(self, model: nn.Module, optimizer, vocab_size: int, max_grad_norm: float,
                  reducer: Optional[GradReducer] = None, use_graph: bool = False, graph_warmup: int = 2,
-                 max_graphs: int = 4, bucket=None, dp_in_graph: bool = True, bucket_rows=None, criterion=None):
+                 max_graphs: int = 4, bucket=None, dp_in_graph: bool = True, bucket_rows=None, criterion=None,
+                 accumulate: Optional[int] = None):
         """criterion: None = ``nn.CrossEntropyLoss(ignore_index=0)`` (train.py:120); or ``nn.CrossEntropyLoss(ignore_index=0,
         label_smoothing=e)`` / ``transformer.Loss.LabelSmoothingLoss(e, vocab_size, ignore_index=0)`` - label smoothing inside
         the same projection + loss node and the same captured graph (functional.ce_spec maps the object to the kernels and
@@ -69,7 +76,25 @@ class TrainStep:
         the averaged weights).  A SKIPPED step (non-finite gradient norm under the guard) is still a call: the Noam rate
         follows the host's ``global_step``, which counts calls, while Adam's bias corrections follow the device step count,
         which counts applied updates.  Data parallelism needs nothing: the norm is taken after the all-reduce, so every rank
-        reaches the same verdict."""
+        reaches the same verdict.
+
+        accumulate: None or 1 = every call is a step (the code and the launches above).  K >= 2 = gradient accumulation: every
+        call is one MICRO-BATCH (forward, loss, backward adding into the flat gradient buffer) and the K-th call of a window
+        also applies the update; :meth:`flush` applies it to a partly filled window (the end of an epoch).  The window's
+        objective is the criterion on the concatenation of its micro-batches: each contributes the SUM of its row losses and the
+        update divides once by the summed denominators - non-ignored tokens (``nn.CrossEntropyLoss``), ``B * l_max`` of every
+        trimmed micro-batch (``LabelSmoothingLoss``'s mean), 1 (its sum) - which live on the device; averaging per-micro-batch
+        means instead is NOT the gradient of the large batch when token counts differ.  The call returns ``(loss, grad_norm)``:
+        this micro-batch's loss in its own normalisation (comparable with a non-accumulating step's) and the norm of the most
+        recent update (0 before the first).  ``self.updated``: this call applied - or, under the guard, skipped - an update;
+        ``self.window_loss`` / ``self.window_nll``: device scalars written when a window closes; ``self.nll`` stays per
+        micro-batch.  ``global_step`` and the Noam rate advance per UPDATE; dropout and SpecAugment masks are drawn per call.
+        Under the non-finite guard a non-finite accumulated norm or a window without a single token skips the WHOLE window
+        (``skipped`` counts one) and the next window starts clean.  After an update the flat gradient buffer holds ZEROS, not the
+        clipped gradient (the update kernel is the next window's zero_grad).  Data parallelism: nothing is exchanged on
+        non-final micro-batches; at the update the gradient sums and the window's sums are all-reduced (SUM), so the update is the
+        token mean over all ranks and micro-batches - unlike the non-accumulating DP step, which averages the ranks' means as
+        Horovod does.  Needs ``model.forward_packed`` and the optimizer's flat arena (ValueError otherwise)."""
         self.model, self.optimizer = model, optimizer
         self.vocab_size, self.max_grad_norm = vocab_size, max_grad_norm
         self.crit = criterion or nn.CrossEntropyLoss(ignore_index=0)          # train.py:120
@@ -112,6 +137,29 @@ class TrainStep:
         self._loss = self._gnorm = None
         self._cut = None
         self._seed = None
+        # gradient accumulation: None = off (accumulate=None / 1 take the code above unchanged)
+        if accumulate is not None and (isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1):
+            raise ValueError("TrainStep: accumulate must be None or an int >= 1, got %r" % (accumulate,))
+        self.accumulate = None if accumulate is None or int(accumulate) == 1 else int(accumulate)
+        self.updated = False
+        self.window_loss = self.window_nll = None
+        if self.accumulate is not None:
+            if not hasattr(model, "forward_packed"):
+                raise ValueError("TrainStep(accumulate=%d): needs a model with forward_packed (the HIP loss path)" % self.accumulate)
+            if getattr(optimizer, "arena", None) is None or not hasattr(optimizer, "_step_window"):
+                raise ValueError("TrainStep(accumulate=%d): needs an optimizer with the flat arena (ScheduledOptim over a model "
+                                 "on the GPU)" % self.accumulate)
+            # every micro-batch runs the smoothed kernels with a device denominator of 1.0: the SUM of its row losses
+            # (CeSpec(1, 0, -1) is the plain criterion: one kernel body with st_ce_fwd / st_ce_bwd)
+            self._acc_norm = "tokens" if self.ce_spec is None else self.ce_spec.norm
+            self._acc_spec = CeSpec(1.0, 0.0, -1, "sum") if self.ce_spec is None else self.ce_spec._replace(norm="sum")
+            self._win = self._win_out = self._win_rows = None      # device state: _stage_window
+            self._win_rows_host = None
+            self._n_acc = 0                                          # micro-batches in the open window (the host counts calls)
+            self._loads = getattr(optimizer, "_state_loads", 0)
+            self._last_cap = None
+            if reducer is not None:
+                reducer.detach()                                     # nothing is exchanged before the update
 
     def _options(self):
         """The optimizer's option token (None for an optimizer without options); raises inside ``optimizer.averaged()``."""
@@ -129,6 +177,8 @@ class TrainStep:
 
     def _stage_denom(self, B: int, l_max: int, device) -> None:
         """Refresh the loss denominator for this batch (an eager fill on the step's stream, only when the value changes)."""
+        if getattr(self, "accumulate", None) is not None:
+            return self._stage_window(B, l_max, device)
         if self.ce_spec is None or self.ce_spec.norm == "tokens":
             return
         d = float(B * l_max) if self.ce_spec.norm == "rows" else 1.0
@@ -137,6 +187,90 @@ class TrainStep:
         elif d != self._ce_denom_host:
             self._ce_denom.fill_(d)
         self._ce_denom_host = d
+
+    # ---- gradient accumulation ----------------------------------------------------------------------
+    def _stage_window(self, B: int, l_max: int, device) -> None:
+        """The window's device state, created on the first call (never inside a capture), and this micro-batch's share of a
+        "rows" denominator.  A fresh window starts with one eager zero_grads: here, and after optimizer.load_state_dict()."""
+        loads = getattr(self.optimizer, "_state_loads", 0)
+        if self._win is None or self._win.device != device or loads != self._loads:
+            if self._win is None or self._win.device != device:
+                self._win = torch.zeros(4, dtype=torch.float32, device=device)        # denominator, loss sum, NLL sum, micro-batches
+                self._win_out = torch.zeros(4, dtype=torch.float32, device=device)    # what st2_window_close leaves
+                self._ce_denom = torch.ones(1, dtype=torch.float32, device=device)    # the kernels' denominator: always 1
+                self._gnorm = torch.zeros((), dtype=torch.float32, device=device)
+                self.window_loss, self.window_nll = self._win_out[0], self._win_out[1]
+                self._win_rows, self._win_rows_host = None, None
+            self._win.zero_()
+            arena_of(self.model).zero_grads()
+            self._n_acc, self._loads = 0, loads
+        if self._acc_norm == "rows":
+            d = float(B * l_max)
+            if self._win_rows is None:
+                self._win_rows = torch.full((1,), d, dtype=torch.float32, device=device)
+            elif d != self._win_rows_host:
+                self._win_rows.fill_(d)
+            self._win_rows_host = d
+
+    def _micro_batch(self, inputs, input_lengths, targets, target_lengths, ground_truth, layouts=None):
+        """One micro-batch of a window: forward, SUM loss, its note in the window, backward ADDING into the flat buffer (no
+        zero_grad, no update) -> this micro-batch's loss in its own normalisation."""
+        self._zero_tails()
+        rng.advance()
+        loss, _ = self.model.forward_packed(inputs, input_lengths, targets, target_lengths, ce_truth=ground_truth, ignore_index=0,
+                                            layouts=layouts, ce_spec=self._acc_spec, ce_denom=self._ce_denom)
+        self.nll = self.model._st_ce_nll
+        sums = self.model._st_ce_sums
+        d = sums[1:2] if self._acc_norm == "tokens" else (self._win_rows if self._acc_norm == "rows" else None)
+        out = nv.accum_note(sums, d, self._win, torch.empty(1, dtype=torch.float32, device=sums.device))
+        with deferred_wgrads(True):
+            self._backward(loss)
+        return out[0]
+
+    def _window_update(self):
+        """Norm + clip + Adam over the window's sum divided by its denominator, then the window's results and a fresh window.
+        (Across ranks the sums were all-reduced, denominator included: nothing is left to scale.)"""
+        gnorm = self.optimizer.step_captured(grad_norm=True, max_norm=self.max_grad_norm, grad_scale=1.0, window=self._win)
+        nv.window_close(self._win, self._win_out)
+        return gnorm
+
+    def _close_window(self):
+        self.global_step += 1
+        self.optimizer.update_learning_rate(self.global_step)
+        red = self.reducer
+        if red is not None and red.active:
+            red.reduce_all(divide=False)             # the rank SUM of the gradient sums ...
+            if red.world > 1:                        # ... and of (denominator, loss sum, NLL sum): the mean over all ranks' tokens.
+                torch.distributed.all_reduce(self._win[:3], op=torch.distributed.ReduceOp.SUM, group=red.group)
+                # (norm "sum": win[0] = 1 on every rank adds up to the world size - the rank average of the sums)
+        self._apply_window()
+
+    def _apply_window(self):
+        """The update of the open window: the captured one behind a replayed micro-batch, else eager."""
+        cap = self._last_cap
+        if cap is not None:
+            cap.g_opt.replay()
+            self._gnorm = cap.gnorm
+        else:
+            self._gnorm = self._window_update()
+        self._n_acc, self.updated = 0, True
+
+    def flush(self):
+        """Apply the update to a partly filled window (the end of an epoch); a no-op when nothing has been accumulated (and
+        without ``accumulate``).  -> (window_loss, grad_norm) or None."""
+        if self.accumulate is None or self._n_acc == 0:
+            return None
+        self._options()
+        self._close_window()
+        return self.window_loss, self._gnorm
+
+    def _accumulate_call(self, batch, inputs, input_lengths, targets, target_lengths, ground_truth):
+        self.updated = False
+        loss, _ = self._dispatch(batch, inputs, input_lengths, targets, target_lengths, ground_truth)
+        self._n_acc += 1
+        if self._n_acc >= self.accumulate:
+            self._close_window()
+        return loss, self._gnorm
 
     # ---- the two halves of a step -------------------------------------------------------------
     @staticmethod
@@ -150,7 +284,7 @@ class TrainStep:
         """The whole step is captured as ONE graph (no data-parallel split into several captures that share a memory pool)."""
         split = self.reducer is not None and self.reducer.active and hasattr(self.model, "forward_packed") \
             and hasattr(self.model, "encoder")
-        return not split or self.dp_in_graph
+        return not split or self.dp_in_graph or self.accumulate is not None      # (a micro-batch is always one graph)
 
     def _forward_backward(self, inputs, input_lengths, targets, target_lengths, ground_truth, captured=False, layouts=None):
         self._zero_tails()
@@ -274,6 +408,9 @@ class TrainStep:
         return grad_norm
 
     def _eager(self, batch, layouts=None):
+        if self.accumulate is not None:
+            self._last_cap = None
+            return self._micro_batch(*batch, layouts=layouts), None
         loss = self._forward_backward(*batch, layouts=layouts)
         scale = self.reducer.synchronize(divide=not self._fold_scale()) if self.reducer is not None else 1.0
         self.optimizer.update_learning_rate(self.global_step)
@@ -283,9 +420,16 @@ class TrainStep:
         """inputs [B, T, F] / targets, ground_truth [B, L] on the GPU; lengths on host or GPU."""
         self._options()
         t_max, l_max = int(input_lengths.max()), int(target_lengths.max())     # host ints when lengths are CPU tensors
-        self.global_step += 1
+        if self.accumulate is None:
+            self.global_step += 1                # (accumulating: counted per update, in _close_window)
         batch = (inputs[:, :t_max], input_lengths, targets[:, :l_max], target_lengths, ground_truth[:, :l_max])
         self._stage_denom(batch[4].shape[0], batch[4].shape[1], inputs.device)      # (label smoothing, norm "rows": B * l_max)
+        if self.accumulate is not None:
+            return self._accumulate_call(batch, inputs, input_lengths, targets, target_lengths, ground_truth)
+        return self._dispatch(batch, inputs, input_lengths, targets, target_lengths, ground_truth)
+
+    def _dispatch(self, batch, inputs, input_lengths, targets, target_lengths, ground_truth):
+        """Eager step, bucket step, or the captured step of this batch signature."""
         if self.bucket is not None:
             return self._bucket_call(*batch)
         if not self.use_graph:
@@ -387,6 +531,11 @@ class TrainStep:
         if cap.options != self._options():
             raise RuntimeError("TrainStep: the optimizer's options changed after this step was captured (the graph holds the "
                                "old launches): enable the guard / the average before the first capture, or build a new TrainStep")
+        if self.accumulate is not None:                   # the micro-batch capture; _close_window replays the update's
+            self._g_fb, self._g_enc, self._g_opt, self._last_cap = cap.g_fb, None, cap.g_opt, cap
+            self.nll = cap.nll
+            cap.g_fb.replay()
+            return cap.loss, None
         self._g_fb, self._g_enc, self._g_opt, self._dec_lo = cap.g_fb, cap.g_enc, cap.g_opt, cap.dec_lo     # (introspection / tests)
         self.nll = cap.nll                                # a static output of the graph, like the loss
         self.optimizer.update_learning_rate(self.global_step)
@@ -440,6 +589,15 @@ class TrainStep:
         # default "global" capture mode that call from ANOTHER thread aborts the process ("operation not permitted
         # when stream is capturing").  With a process group alive, only this thread's unsafe calls are policed.
         mode = dict(capture_error_mode="thread_local") if torch.distributed.is_initialized() else {}
+        if self.accumulate is not None:
+            # two captures from one pool: the micro-batch (no zero_grad, no update), and the update (norm, clip + Adam, close);
+            # with data parallelism the collectives run eagerly between them (_close_window)
+            with torch.cuda.graph(cap.g_fb, pool=pool, **mode):
+                cap.loss = self._micro_batch(*batch, layouts=layouts)
+                cap.nll = self.nll
+            with torch.cuda.graph(cap.g_opt, pool=pool, **mode):
+                cap.gnorm = self._window_update()
+            return cap
         if split and self.dp_in_graph:
             # ONE graph: forward + loss + decoder backward | decoder-side buckets start on RCCL's stream (a forked branch
             # of the graph) | encoder backward runs beside them | remaining buckets | join | clip + Adam

@@ -24,7 +24,10 @@ class ScheduledOptim(object):
         ``skipped`` (the running count) are device scalars: read them when you choose, e.g. once per epoch.
       * ``enable_averaging(decay, warmup)`` (config keys ``ema_decay``, ``ema_warmup``): an exponential moving average of the
         weights, kept by the update kernel in the same pass; ``with optimizer.averaged():`` puts it under the model.
-    With either enabled ``state_dict()`` carries one extra top-level key, ``"averaging"``."""
+    With either enabled ``state_dict()`` carries one extra top-level key, ``"averaging"``.
+
+    ``step_captured(..., window=win)`` is the update of a gradient-accumulation window (``st_amd.trainer.TrainStep(accumulate=K)``):
+    the gradient buffer holds a sum whose denominator is the device scalar ``win[0]``; both options work inside it."""
 
     _allow_cpu_arena = False     # tests/_emul.py: exercise the arena path with emulated kernels on the CPU
 
@@ -55,6 +58,7 @@ class ScheduledOptim(object):
         self._avg_opts = None        # (decay, warmup) once averaging is on; the buffer is arena.avg
         self._avg_extra = []         # [(tensor, its average)] outside the arena (JointTrainStep: the CTC head)
         self._in_averaged = False
+        self._state_loads = 0        # load_state_dict() calls (an accumulating TrainStep starts a fresh window after one)
         # optional keys: a reference config without them builds exactly the object above
         if getattr(config, "skip_nonfinite", None):
             self.enable_nonfinite_guard()
@@ -172,7 +176,34 @@ class ScheduledOptim(object):
             self._norm_scratch = nv.grad_norm_scratch(device)
         return self._norm_scratch
 
-    def step_captured(self, grad_norm=None, max_norm=None, grad_scale=1.0):
+    def _step_window(self, grad_norm, max_norm, grad_scale, win):
+        """The update of an accumulation window: ``st2_grad_norm_win`` + ``st2_adam_clip_win``.  The flat gradient buffer holds
+        the SUM over the window's micro-batches and ``win`` (device f32 [4]) its denominator in win[0]: the norm returned and
+        the gradient Adam consumes are those of ``grad_scale * g / win[0]``.  With the guard on, a non-finite norm or a
+        denominator <= 0 skips the update.  Either way the gradient buffer holds ZEROS afterwards, not the clipped gradient."""
+        if self.arena is None or not self._plain():
+            raise ValueError("ScheduledOptim.step_captured(window=): needs the flat-arena HIP update (the model on the GPU, no "
+                             "weight decay / amsgrad / maximize)")
+        if grad_norm is not True or max_norm is None:
+            raise ValueError("ScheduledOptim.step_captured(window=): takes grad_norm=True and a max_norm (the norm of a window "
+                             "is computed here, over the divided sum)")
+        if self._in_averaged:
+            raise RuntimeError("ScheduledOptim.step_captured: inside averaged() the model holds the averaged weights")
+        from st_amd import native as nv
+        group = self.optimizer.param_groups[0]
+        p, st = self._flat_state()
+        self.norm_scratch(p.device)
+        out = torch.empty((), dtype=torch.float32, device=p.device)
+        gnorm = nv.grad_norm_win(p.grad, self._norm_scratch, out, st["step"], self._guard, win, grad_scale=grad_scale)
+        averaging = self._avg_opts is not None
+        decay, warmup = self._avg_opts if averaging else (1.0, False)
+        beta1, beta2 = group["betas"]
+        nv.adam_clip_win(p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], self.lr_tensor, st["step"], gnorm, max_norm, beta1, beta2,
+                         group["eps"], win, grad_scale=grad_scale, found_inf=self.found_inf,
+                         avg=self.arena.avg if averaging else None, decay=decay, decay_warmup=warmup)
+        return gnorm
+
+    def step_captured(self, grad_norm=None, max_norm=None, grad_scale=1.0, window=None):
         """The update alone (rate already set with update_learning_rate) - what a HIP graph captures.
         With ``grad_norm`` and ``max_norm`` on the flat-arena path, gradient clipping (train.py:45) and the Adam update are
         two launches over the buffers: ``st_grad_norm`` (the global norm; also advances the step count) and
@@ -181,7 +212,10 @@ class ScheduledOptim(object):
         grad_scale: the gradient buffer still has to be multiplied by this (st_amd.dp.GradReducer.synchronize(divide=False)
         leaves the rank SUM and returns 1 / world): folded into the norm and the clip coefficient - no pass of its own.
         With the guard or the average enabled the two launches are ``st2_grad_norm_guard`` and ``st2_adam_clip_avg``; a norm
-        handed in (the joint step) gives the verdict through torch ops on that scalar - no host read either way."""
+        handed in (the joint step) gives the verdict through torch ops on that scalar - no host read either way.
+        window: the device f32 [4] state of a gradient-accumulation window - see :meth:`_step_window`."""
+        if window is not None:
+            return self._step_window(grad_norm, max_norm, grad_scale, window)
         group = self.optimizer.param_groups[0]
         plain = not (group["weight_decay"] or group["amsgrad"] or group["maximize"])
         guard, averaging = self._guard is not None, self._avg_opts is not None
@@ -275,6 +309,7 @@ class ScheduledOptim(object):
         return out
 
     def load_state_dict(self, optimizer_state_dict):
+        self._state_loads += 1
         if self.arena is None:
             return self.optimizer.load_state_dict(optimizer_state_dict)
         groups = optimizer_state_dict["param_groups"]
