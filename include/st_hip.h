@@ -565,7 +565,13 @@ int st_attn_probs(st_stream_t stream, const void* Q, int ldq, const void* K, int
  * closes the module boundary.  Padded layout: utterance b owns query rows b Lq .. of Q / O / dO / dQ and key rows b Lk .. of
  * K / V / dK / dV; head h = columns h d_k ..; d_k % 8 == 0.  mask: uint8 [B, Lq, Lk], nonzero = masked (NULL: none); a row
  * with every key masked yields a zero context and zero gradients (the reference: NaN).  lse / delta: f32 [H, B Lq] (natural
- * log); P (nullable, f32 [B, H, Lq, Lk]): the probabilities before dropout (Attention.py:96).  drop_*: as everywhere. */
+ * log); P (nullable, f32 [B, H, Lq, Lk]): the probabilities before dropout (Attention.py:96).  drop_*: as everywhere.
+ * Limits: a workgroup keeps one query's scores (one key's, on the key side of the backward) in 64 KiB = 16384 floats of LDS -
+ *   st_attn_dense_fwd                Lk + 5 d_k + 4   <= 16384
+ *   st_attn_dense_bwd, query side    2 Lk + 6 d_k + 4 <= 16384
+ *   st_attn_dense_bwd, key side      2 Lq + 10 d_k    <= 16384
+ * - and B H max(Lq, Lk) < 2^31; beyond them the call returns -3 and launches nothing.  The backward's range is the smaller one:
+ * a caller that will differentiate checks all three before the forward (st_amd.native.attn_dense_check). */
 int st_attn_dense_fwd(st_stream_t stream, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv,
                       const unsigned char* mask, void* O, int ldo, float* lse, float* P, int B, int H, int d_k, int Lq, int Lk,
                       float scale, const unsigned* drop_seed, unsigned drop_salt, int drop_thresh, float drop_scale);

@@ -1014,10 +1014,14 @@ class DenseMhaFn(torch.autograd.Function):
     LayerNorm.  Padded layouts only; rows are [B Lq] / [B Lk]."""
 
     @staticmethod
-    def forward(ctx, xq, xk, xv, anchor, mod, mask, B, Lq, Lk, drop=None, want_attn=False):
+    def forward(ctx, xq, xk, xv, anchor, mod, mask, B, Lq, Lk, drop=None, want_attn=False, grad_mode=True):
+        """grad_mode: torch.is_grad_enabled() of the CALLER (always off in here, while needs_input_grad ignores it)."""
         s = mod._st
         d, H = s.d_model, s.n_head
         scale = 1.0 / math.sqrt(d // H)
+        # st_attn_dense_bwd keeps twice the scores in LDS: a forward it could not differentiate is refused here, before any launch,
+        # not inside autograd.backward (under torch.no_grad nothing needs a gradient: the forward's larger range holds)
+        nv.attn_dense_check(d // H, Lq, Lk, backward=bool(grad_mode) and any(ctx.needs_input_grad))
         Q, K, V = _empty(B * Lq, d, xq), _empty(B * Lk, d, xq), _empty(B * Lk, d, xq)
         nv.gemm(xq, s.w_q, Q, bias=s.b_q)
         nv.gemm(xk, s.w_kv[:d], K, bias=s.b_kv[:d])
@@ -1058,7 +1062,7 @@ class DenseMhaFn(torch.autograd.Function):
         dgrad(dK, s.w_kv[:d], dxk)
         dgrad(dV, s.w_kv[d:], dxv)
         arena.grads_ready(s.lo, s.hi)
-        return dxq, dxk, dxv, None, None, None, None, None, None, None, None
+        return dxq, dxk, dxv, None, None, None, None, None, None, None, None, None
 
 
 class FfnFn(torch.autograd.Function):

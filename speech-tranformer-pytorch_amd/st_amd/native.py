@@ -1087,14 +1087,20 @@ def ctc_loss_grad(lp, classes, in_len, tgt_len, coef, ws, nll, g, roww, softmax_
     return g
 
 
-def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False):
+def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False, out=None):
     """The attention probabilities of one sublayer, materialised: f32 [B, n_head, Lq, Lk] (zeros at masked keys and in the
-    rows of padding positions).  Q, K: bf16 row matrices (column slices of the q | k | v projection are fine)."""
+    rows of padding positions).  Q, K: bf16 row matrices (column slices of the q | k | v projection are fine).  out: the
+    caller's contiguous f32 [B, n_head, Lq, Lk] buffer (None: a new one).  One workgroup per query holds its scores in LDS:
+    Lk + d_k + 8 <= 16384 floats (64 KiB), else ValueError (code -3)."""
     for t, nm in ((Q, "Q"), (K, "K")):
         _mat(t, BF16, nm)
     B = q_off.numel()
     d_k = Q.shape[1] // n_head
-    P = torch.empty(B, n_head, int(Lq), int(Lk), dtype=F32, device=Q.device)
+    if out is None:
+        P = torch.empty(B, n_head, int(Lq), int(Lk), dtype=F32, device=Q.device)
+    else:
+        P = out
+        _dev(P, F32, (B, n_head, int(Lq), int(Lk)), "attn_probs: out")
     _tag("attn_probs", B, n_head, d_k, int(Lq), int(Lk))
     rc = load().st_attn_probs(_stream(), Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), P.data_ptr(), q_off.data_ptr(),
                               q_len.data_ptr(), k_off.data_ptr(), k_len.data_ptr(), B, n_head, d_k, int(Lq), int(Lk), int(causal),
@@ -1103,9 +1109,43 @@ def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, 
     return P
 
 
-def attn_dense_fwd(Q, K, V, mask, O, lse, B, n_head, Lq, Lk, scale, drop=None, want_probs=False):
+# The dense kernels keep one query's scores (forward, query side of the backward) or one key's (key side) in LDS, 64 KiB = 16384
+# floats per workgroup (include/st_hip.h, st_attn_dense_*):
+ATTN_DENSE_LDS_FLOATS = 16384
+
+
+def attn_dense_lds_floats(d_k, Lq, Lk):
+    """The floats of LDS per workgroup of (the forward, the backward's query side, the backward's key side)."""
+    return Lk + 5 * d_k + 4, 2 * Lk + 6 * d_k + 4, 2 * Lq + 10 * d_k
+
+
+def attn_dense_check(d_k, Lq, Lk, backward=True):
+    """ValueError unless attn_dense_fwd - and, with ``backward``, attn_dense_bwd - accepts these extents:
+        forward                Lk + 5 d_k + 4      <= 16384
+        backward, query side   2 Lk + 6 d_k + 4    <= 16384
+        backward, key side     2 Lq + 10 d_k       <= 16384
+    A forward that will be differentiated is checked against all three BEFORE anything is launched (functional.DenseMhaFn), so
+    that the refusal does not surface inside autograd.backward; an inference call keeps the forward's larger range."""
+    fwd, bq, bk = attn_dense_lds_floats(int(d_k), int(Lq), int(Lk))
+    lim = ATTN_DENSE_LDS_FLOATS
+    bad = []
+    if fwd > lim:
+        bad.append("the forward needs Lk + 5 d_k + 4 = %d" % fwd)
+    if backward and bq > lim:
+        bad.append("the backward's query side needs 2 Lk + 6 d_k + 4 = %d" % bq)
+    if backward and bk > lim:
+        bad.append("the backward's key side needs 2 Lq + 10 d_k = %d" % bk)
+    if bad:
+        raise ValueError("dense attention: Lq = %d, Lk = %d, d_k = %d exceed the limit of %d floats (64 KiB) of LDS per workgroup: %s"
+                         % (Lq, Lk, d_k, lim, "; ".join(bad)))
+
+
+def attn_dense_fwd(Q, K, V, mask, O, lse, B, n_head, Lq, Lk, scale, drop=None, want_probs=False, probs=None):
     """Attention under an arbitrary dense mask (uint8 [B, Lq, Lk], nonzero = masked; None = no mask) over padded row matrices
-    Q [B Lq, H d_k], K / V [B Lk, H d_k] (see st_attn_dense_fwd: the slow general path).  -> P (f32 [B, H, Lq, Lk]) or None."""
+    Q [B Lq, H d_k], K / V [B Lk, H d_k] (see st_attn_dense_fwd: the slow general path).  -> P (f32 [B, H, Lq, Lk], the
+    probabilities BEFORE dropout; ``probs``: the caller's contiguous buffer for them, which implies want_probs) or None.
+    Limit: Lk + 5 d_k + 4 <= 16384 floats of LDS, else ValueError (code -3); attn_dense_bwd's limits are tighter -
+    attn_dense_check(d_k, Lq, Lk) tells before the forward runs."""
     for t, nm in ((Q, "Q"), (K, "K"), (V, "V"), (O, "O")):
         _mat(t, BF16, nm)
     d_k = Q.shape[1] // n_head
@@ -1114,7 +1154,11 @@ def attn_dense_fwd(Q, K, V, mask, O, lse, B, n_head, Lq, Lk, scale, drop=None, w
     if Q.shape[0] != B * Lq or K.shape[0] != B * Lk or V.shape[0] != B * Lk:
         raise ValueError("attn_dense_fwd: padded layouts expected (B Lq query rows, B Lk key rows)")
     _vec(lse, F32, n_head * B * Lq, "lse")
-    P = torch.empty(B, n_head, Lq, Lk, dtype=F32, device=Q.device) if want_probs else None
+    if probs is not None:
+        P = probs
+        _dev(P, F32, (B, n_head, Lq, Lk), "attn_dense_fwd: probs")
+    else:
+        P = torch.empty(B, n_head, Lq, Lk, dtype=F32, device=Q.device) if want_probs else None
     _tag("attn_dense", B, n_head, d_k, Lq, Lk)
     rc = load().st_attn_dense_fwd(_stream(), Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0), _p(mask),
                                   O.data_ptr(), O.stride(0), lse.data_ptr(), _p(P), B, n_head, d_k, int(Lq), int(Lk), float(scale),
@@ -1124,6 +1168,9 @@ def attn_dense_fwd(Q, K, V, mask, O, lse, B, n_head, Lq, Lk, scale, drop=None, w
 
 
 def attn_dense_bwd(Q, K, V, mask, dO, lse, delta, dQ, dK, dV, B, n_head, Lq, Lk, scale, drop=None):
+    """The backward of attn_dense_fwd (same Q, K, V, mask, drop; lse from the forward): writes delta (f32 [H, B Lq]), dQ, dK, dV.
+    Limits: 2 Lk + 6 d_k + 4 <= 16384 (query side) and 2 Lq + 10 d_k <= 16384 (key side) floats of LDS, else ValueError (code -3)
+    with nothing launched."""
     for t, nm in ((Q, "Q"), (K, "K"), (V, "V"), (dO, "dO"), (dQ, "dQ"), (dK, "dK"), (dV, "dV")):
         _mat(t, BF16, nm)
     d_k = Q.shape[1] // n_head

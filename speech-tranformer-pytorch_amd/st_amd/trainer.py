@@ -34,6 +34,8 @@ the next window.  In graph mode the micro-batch and the update are two captures.
 from __future__ import annotations
 
 import collections
+import contextlib
+import gc
 import os
 import time
 from typing import Optional
@@ -47,6 +49,25 @@ from .dp import GradReducer
 from . import rng
 from . import native as nv
 from .functional import CeSpec, TailBuffers, ce_spec, deferred_wgrads
+
+
+@contextlib.contextmanager
+def no_gc_inside_capture():
+    """Around the captures of a step: collect garbage BEFORE them and keep the collector off until they have ended.
+
+    A generational pass that happens to fire inside ``with torch.cuda.graph(...)`` runs destructors in the middle of a stream
+    capture - those of a dead TrainStep's graphs and private pool, say, left in a reference cycle by an earlier step object
+    - and the process aborted there (main thread, inside the collector, inside the micro-batch capture).  torch.cuda.graph used
+    to call gc.collect() on entry; it no longer does unless torch.compiler.config.force_cudagraph_gc is set, so when a pass
+    fires is a matter of how many objects the process happens to have allocated."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 def clip_grad_norm_flat(arena, max_norm: float) -> torch.Tensor:
@@ -552,6 +573,10 @@ class TrainStep:
         return cap.loss, cap.gnorm
 
     def _capture(self, batch, layouts=None):
+        with no_gc_inside_capture():
+            return self._capture_graphs(batch, layouts)
+
+    def _capture_graphs(self, batch, layouts=None):
         if hasattr(self.optimizer, "_flat_state") and getattr(self.optimizer, "arena", None) is not None:
             self.optimizer._flat_state()      # Adam's lazily created state must exist BEFORE the capture (a captured
                                               # zero-fill would reset it on every replay)
@@ -942,12 +967,13 @@ class JointTrainStep:
             torch.cuda.synchronize()
             pool = torch.cuda.graph_pool_handle()
             ga1, ga2, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ga1, pool=pool):
-                enc, lp = self._part_a1(batch, plan, layouts)
-            with torch.cuda.graph(ga2, pool=pool):
-                att, enc_in = self._part_a2(batch, enc, layouts)
-            with torch.cuda.graph(gb, pool=pool):
-                gnorm = self._part_b(enc, enc_in, lp, plan)
+            with no_gc_inside_capture():
+                with torch.cuda.graph(ga1, pool=pool):
+                    enc, lp = self._part_a1(batch, plan, layouts)
+                with torch.cuda.graph(ga2, pool=pool):
+                    att, enc_in = self._part_a2(batch, enc, layouts)
+                with torch.cuda.graph(gb, pool=pool):
+                    gnorm = self._part_b(enc, enc_in, lp, plan)
             self._cap = (ga1, ga2, gb, att, lp, gnorm)
         ga1, ga2, gb, att, lp, gnorm = self._cap
         ga1.replay()
@@ -974,7 +1000,7 @@ class JointTrainStep:
             plan.loss_workspace()                 # alpha / beta belong to the plan, not to the graph's pool
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with no_gc_inside_capture(), torch.cuda.graph(graph):
                 out = self._step_hip(batch, plan, layouts)
             self._cap = (graph, out)
         graph, out = self._cap

@@ -122,7 +122,8 @@ class MultiHeadAttention(nn.Module):
         arena = arena_of(self)
         with arena.scope():
             args = [t.reshape(-1, d).to(torch.bfloat16) for t in (q, k, v)]
-            res = F_.DenseMhaFn.apply(*args, self.linear_q.weight, self, m8, B, Lq, Lk, self._drop(q.device), bool(self.return_attn))
+            res = F_.DenseMhaFn.apply(*args, self.linear_q.weight, self, m8, B, Lq, Lk, self._drop(q.device), bool(self.return_attn),
+                                      torch.is_grad_enabled())
         out, attns = res if self.return_attn else (res, None)
         return out.to(q.dtype).view(B, Lq, d), attns
 

@@ -442,41 +442,43 @@ def attn_bwd(Q, K, V, O, dO, lse, delta, dQ, dK, dV, q_off, q_len, k_off, k_len,
             dV[ks, cs] = (pv.to(BF16).to(dtype).t() @ do).to(BF16)
 
 
-def _dense_core(Q, K, V, mask, b, h, n_head, Lq, Lk, scale, drop):
+def _dense_core(Q, K, V, mask, b, h, n_head, Lq, Lk, scale, drop, dtype=F32):
     dk = Q.shape[1] // n_head
     cs = slice(h * dk, (h + 1) * dk)
     qs, ks = slice(b * Lq, (b + 1) * Lq), slice(b * Lk, (b + 1) * Lk)
-    q, k, v = Q[qs, cs].float(), K[ks, cs].float(), V[ks, cs].float()
+    q, k, v = Q[qs, cs].to(dtype), K[ks, cs].to(dtype), V[ks, cs].to(dtype)
     s = q @ k.t() * scale
     if mask is not None:
         s = s.masked_fill(mask[b].bool(), float("-inf"))
     dead = torch.isinf(s).all(-1, keepdim=True)                 # every key masked: zero context, zero gradients
     p = torch.where(dead, torch.zeros_like(s), torch.softmax(torch.where(dead, torch.zeros_like(s), s), -1))
-    keep = keep_qk(drop, b * n_head + h, Lq, Lk).float() * drop.scale if _on(drop) else torch.ones_like(p)
+    keep = keep_qk(drop, b * n_head + h, Lq, Lk).to(dtype) * drop.scale if _on(drop) else torch.ones_like(p)
     return q, k, v, s, p, keep, qs, ks, cs, dead
 
 
-def attn_dense_fwd(Q, K, V, mask, O, lse, B, n_head, Lq, Lk, scale, drop=None, want_probs=False):
-    P = torch.zeros(B, n_head, Lq, Lk) if want_probs else None
+def attn_dense_fwd(Q, K, V, mask, O, lse, B, n_head, Lq, Lk, scale, drop=None, want_probs=False, probs=None, dtype=F32):
+    """The dense kernels keep P and dS in fp32 and round only their bf16 outputs: no rounding point in between.  probs: the
+    caller's [B, H, Lq, Lk] buffer for P (implies want_probs)."""
+    P = probs if probs is not None else (torch.zeros(B, n_head, Lq, Lk, dtype=dtype) if want_probs else None)
     for b in range(B):
         for h in range(n_head):
-            q, k, v, s, p, keep, qs, ks, cs, dead = _dense_core(Q, K, V, mask, b, h, n_head, Lq, Lk, scale, drop)
+            q, k, v, s, p, keep, qs, ks, cs, dead = _dense_core(Q, K, V, mask, b, h, n_head, Lq, Lk, scale, drop, dtype)
             O[qs, cs] = ((p * keep) @ v).to(BF16)
             l = torch.logsumexp(torch.where(dead, torch.zeros_like(s), s), -1)
-            lse.view(n_head, B * Lq)[h, qs] = torch.where(dead.squeeze(-1), torch.full_like(l, float("inf")), l)
+            lse.view(n_head, B * Lq)[h, qs] = torch.where(dead.squeeze(-1), torch.full_like(l, float("inf")), l).to(lse.dtype)
             if P is not None:
-                P[b, h] = p
+                P[b, h] = p.to(P.dtype)
     return P
 
 
-def attn_dense_bwd(Q, K, V, mask, dO, lse, delta, dQ, dK, dV, B, n_head, Lq, Lk, scale, drop=None):
+def attn_dense_bwd(Q, K, V, mask, dO, lse, delta, dQ, dK, dV, B, n_head, Lq, Lk, scale, drop=None, dtype=F32):
     for b in range(B):
         for h in range(n_head):
-            q, k, v, s, p, keep, qs, ks, cs, dead = _dense_core(Q, K, V, mask, b, h, n_head, Lq, Lk, scale, drop)
-            do = dO[qs, cs].float()
+            q, k, v, s, p, keep, qs, ks, cs, dead = _dense_core(Q, K, V, mask, b, h, n_head, Lq, Lk, scale, drop, dtype)
+            do = dO[qs, cs].to(dtype)
             dp = (do @ v.t()) * keep
             dl = (p * dp).sum(-1, keepdim=True)
-            delta.view(n_head, B * Lq)[h, qs] = dl.squeeze(-1)
+            delta.view(n_head, B * Lq)[h, qs] = dl.squeeze(-1).to(delta.dtype)
             ds = p * (dp - dl)
             dQ[qs, cs] = (ds @ k * scale).to(BF16)
             dK[ks, cs] = (ds.t() @ q * scale).to(BF16)
@@ -508,10 +510,10 @@ def ctc_dlogits(logits, lse, rowmap, T, roww, scat, gsmall, grad_out, dlogits, V
         dlogits[r, sc[keep].long()] = (g[int(rowmap[r])][keep] * grad_out.reshape(())).to(BF16)
 
 
-def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False, dtype=F32):
+def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False, out=None, dtype=F32):
     B = q_off.numel()
     d_k = Q.shape[1] // n_head
-    P = torch.zeros(B, n_head, int(Lq), int(Lk), dtype=dtype)
+    P = torch.zeros(B, n_head, int(Lq), int(Lk), dtype=dtype) if out is None else out.zero_()
     for b in range(B):
         lq, lk, qo, ko = int(q_len[b]), int(k_len[b]), int(q_off[b]), int(k_off[b])
         for h in range(n_head):
@@ -520,7 +522,7 @@ def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, 
             s = q @ k.t() * (math.log(2.0) if k_prescaled else scale)
             if causal:
                 s = s.masked_fill(torch.ones(lq, lk, dtype=torch.bool).triu(1), float("-inf"))
-            P[b, h, :lq, :lk] = torch.softmax(s, -1)
+            P[b, h, :lq, :lk] = torch.softmax(s, -1).to(P.dtype)
     return P
 
 

@@ -492,3 +492,36 @@ def test_two_ranks_accumulate_the_token_mean_over_all_ranks(golden_dir):
     with emulated_kernels():          # (the arena's layout of the parameters: offsets only)
         compare_grads(_build(w), torch.from_numpy(g_eff), truth["grads"])
     assert abs(wloss - truth["loss"]) <= 2e-2 * truth["loss"] and abs(gnorm - truth["gnorm"]) <= 2e-2 * truth["gnorm"]
+
+
+# ---- 8. the garbage collector stays out of a capture ------------------------------------------------------------------------------
+def test_no_garbage_collection_inside_a_capture():
+    """trainer.no_gc_inside_capture (around every capture of TrainStep / JointTrainStep): dead cycles are collected BEFORE the
+    capture begins, no generational pass can fire inside it, and the collector's state is what it was afterwards - also when
+    the capture raises, and also when it was off to begin with."""
+    import gc
+    import weakref
+    from st_amd.trainer import no_gc_inside_capture
+
+    class Node:
+        pass
+
+    a, b = Node(), Node()
+    a.other, b.other = b, a                       # a dead cycle, as a discarded step object leaves behind
+    alive = weakref.ref(a)
+    del a, b
+    assert gc.isenabled()
+    with no_gc_inside_capture():
+        assert alive() is None and not gc.isenabled()
+    assert gc.isenabled()
+    with pytest.raises(RuntimeError):
+        with no_gc_inside_capture():
+            raise RuntimeError("the capture failed")
+    assert gc.isenabled()
+    gc.disable()
+    try:
+        with no_gc_inside_capture():
+            assert not gc.isenabled()
+        assert not gc.isenabled()
+    finally:
+        gc.enable()

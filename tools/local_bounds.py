@@ -1,6 +1,7 @@
 """Where the local bounds of tests/test_kernels_gpu.py come from (tests/LOCAL_BOUNDS.md): on the CPU, every emulation of
 tests/_emul.py evaluated with fp32 and with fp64 accumulation - same bf16 rounding points - over the kernel tests' own cases;
-the largest per-row / per-column / per-element ratio of tests/_local.py per family and output.  No kernel runs here.
+the largest per-row / per-column / per-element ratio of tests/_local.py per family and output; likewise the slow-path attention
+kernels over the cases of tests/test_slow_attention_gpu.py (families "dense" and "probs").  No kernel runs here.
 
     python tools/local_bounds.py            # prints one line per family / output
 """
@@ -17,6 +18,7 @@ for p in (ROOT, os.path.join(ROOT, "speech-tranformer-pytorch_amd")):
 
 from st_amd import chains, native as nv          # noqa: E402
 from tests import _emul as em                     # noqa: E402
+from tests import _slow_attn as sa                # noqa: E402
 from tests import test_kernels_gpu as tk          # noqa: E402
 from tests._local import local_figures            # noqa: E402
 
@@ -174,6 +176,45 @@ def probs_and_ctc():
         note("ctc_dlogits", "dlogits", out[F32][:, :V], out[F64][:, :V])
 
 
+def dense():
+    """The slow-path attention kernels over the cases of tests/test_slow_attention_gpu.py (tests/_slow_attn.py).  They have no
+    bf16 rounding point between their inputs and their outputs, so the fp32 outputs lse / delta / P follow the rule (the emulation
+    in fp32 against fp64); the bf16 outputs are single-rounding outputs (L_BF16) - their row "(bf16 vs fp64)" is the once-rounded
+    emulation against the UNROUNDED fp64 reference of tests/_attn_ref.py: the room the rounding alone takes of the bound."""
+    for _, kw in sa.dense_cases() + [(n, k) for n, k, _, _ in sa.lds_cases()]:
+        c = sa.build(**kw)
+        drop = sa.CPU.drop(c)
+        res = {}
+        for dt in (F32, F64):
+            n = c.H * c.B * c.Lq
+            r = dict(O=torch.zeros(c.B * c.Lq, c.d, dtype=BF16), lse=torch.zeros(n, dtype=dt), delta=torch.zeros(n, dtype=dt),
+                     dQ=torch.zeros(c.B * c.Lq, c.d, dtype=BF16), dK=torch.zeros(c.B * c.Lk, c.d, dtype=BF16),
+                     dV=torch.zeros(c.B * c.Lk, c.d, dtype=BF16))
+            r["P"] = em.attn_dense_fwd(c.Q, c.K, c.V, c.mask, r["O"], r["lse"], c.B, c.H, c.Lq, c.Lk, c.scale, drop=drop, want_probs=True, dtype=dt)
+            if c.dO is not None:
+                em.attn_dense_bwd(c.Q, c.K, c.V, c.mask, c.dO, r["lse"], r["delta"], r["dQ"], r["dK"], r["dV"], c.B, c.H, c.Lq, c.Lk, c.scale,
+                                  drop=drop, dtype=dt)
+            res[dt] = r
+        live = torch.isfinite(res[F64]["lse"])                        # (a dead row's lse is +inf on both sides: compared exactly)
+        note("dense", "lse", res[F32]["lse"][live], res[F64]["lse"][live])
+        note("dense", "P", res[F32]["P"], res[F64]["P"])
+        if c.dO is not None:
+            note("dense", "delta", res[F32]["delta"], res[F64]["delta"])
+        for nm in ("O", "dQ", "dK", "dV"):
+            if c.ref[nm] is not None:
+                note("dense (bf16 vs fp64)", nm, res[F32][nm], c.ref[nm])
+
+
+def probs():
+    """st_attn_probs over the cases of tests/test_slow_attention_gpu.py: the emulation's fp32 maps against the fp64 reference."""
+    for kw in sa.probs_cases():
+        c = sa.build_probs(**kw)
+        ti = lambda v: torch.tensor(v, dtype=I32)
+        P = em.attn_probs(c.Q, c.K, ti(c.q_off), ti(c.q_len), ti(c.k_off), ti(c.k_len), c.H, c.Lq, c.Lk, c.causal, c.scale,
+                          k_prescaled=c.prescaled)
+        note("probs", "P", P, c.ref)
+
+
 def losses():
     R, V = 1206, 4337
     vp = (V + 7) // 8 * 8
@@ -215,6 +256,8 @@ if __name__ == "__main__":
     chain_bwd()
     chain512_bwd()
     probs_and_ctc()
+    dense()
+    probs()
     losses()
     for (family, name, axis), v in sorted(worst.items()):
         print("%-28s %-8s %-8s worst ratio %.3e   x3 = %.3e" % (family, name, axis, v, 3 * v))
