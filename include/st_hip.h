@@ -337,6 +337,10 @@ int st_attn_sf1_fwd(st_stream_t stream, const void* qkv_q, const void* qkv_k, co
  * Q, K, V, O, dO, lse; `delta` is f32 [H, q_rows_total] scratch.  Two kernels:
  * parts & 1 = dQ (also writes delta), parts & 2 = dK/dV (reads delta); 3 = both.
  * O == NULL: delta is an input (st_gemm ST_EPI_BF16_DELTA wrote it with dO) and parts == 3 runs as ONE launch.
+ * k_prescaled as st_attn_fwd.  It also selects the kernel: long non-causal problems with 64-wide heads (max_q, max_k > 128,
+ * O == NULL) run the hand-scheduled streams of csrc/st_attn_bwd64.hip ONLY with k_prescaled = 1; with plain keys the general
+ * kernels serve them (they scale the fp32 score; the streams would scale a bf16 operand and round it again - 2-4x the error
+ * at the scores of a trained model, profiles/attn_sharp_accuracy_before.txt).  Same results contract either way.
  * work_q / work_k: optional work lists (see st_attn_fwd) over query tiles
  * (dQ kernel) and key tiles (dK/dV kernel) of st_attn_tile_rows(1 / 2, ...) rows. */
 int st_attn_bwd(st_stream_t stream, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv,

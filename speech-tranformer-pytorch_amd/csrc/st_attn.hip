@@ -639,9 +639,12 @@ bool fwd_long64(int d_k, int max_q, int max_k, int causal) {
 }
 
 // ... and the hand-scheduled backward of st_attn_bwd64.hip (delta supplied by the producer of dO).  ST_ATTN_BWD64=0 keeps the
-// general kernels, =e the streams in eval mode only (no dropout variant)
-bool bwd_long64(int d_k, int max_q, int max_k, int causal, bool drop) {
-  if (!(d_k == 64 && !causal && max_q > 128 && max_k > 128 && attn_impl() != 1)) return false;
+// general kernels, =e the streams in eval mode only (no dropout variant).  PRE-SCALED KEYS ONLY: with plain keys (c2 != 1) the
+// streams multiply their register-resident operand by scale * log2 e and round it to bf16 a second time (scaled8 - K in the dQ
+// body, Q in the dK/dV body: a different perturbation of every score in each), 1.9-4x the general kernels' error at the scores
+// of a trained model (profiles/attn_sharp_accuracy_before.txt); the general kernels scale the fp32 score and take plain keys instead
+bool bwd_long64(int d_k, int max_q, int max_k, int causal, bool drop, int k_prescaled) {
+  if (!(k_prescaled && d_k == 64 && !causal && max_q > 128 && max_k > 128 && attn_impl() != 1)) return false;
   const int mode = attn_env().bwd64;
   return mode == 0 || (mode == 2 && !drop);
 }
@@ -805,7 +808,7 @@ extern "C" int st_attn_bwd(hipStream_t stream, const void* Q, int ldq, const voi
   dim3 block(256);
   const bool ks2 = key_split(max_q, max_k, causal);
   const bool run_q = (parts & 1) && !(work_q && n_work_q <= 0), run_k = (parts & 2) && !(work_k && n_work_k <= 0);
-  if (O == nullptr && (run_q || run_k) && !ks2 && bwd_long64(d_k, max_q, max_k, causal, drop) && lddq % 8 == 0) {
+  if (O == nullptr && (run_q || run_k) && !ks2 && bwd_long64(d_k, max_q, max_k, causal, drop, k_prescaled) && lddq % 8 == 0) {
     AttnArgs ak = a;
     const int nq = run_q ? plan(a, work_q, n_work_q, B, H, max_q) : 0, nk = run_k ? plan(ak, work_k, n_work_k, B, H, max_k) : 0;
 #ifdef ST_DEV_TRACE      // development builds only (ST_DEV_TRACE=1 python -m st_amd.build): per-workgroup clock stamps, tools/dev/attn_bwd64_trace.py

@@ -847,11 +847,16 @@ class MhaFn(torch.autograd.Function):
         else:
             # non-causal self-attention (an encoder layer on the per-GEMM path: config 3's width, the stand-alone module): the
             # projection hands the attention kernels PRE-SCALED keys, as the encoder's row chains do (chains.EncoderChains)
-            # (pre-scaled keys on the per-GEMM path go through st_gemm's column-range epilogue; where the weight-stationary
-            # st_gemm_ws serves the projection - width 256, encoder-sized row counts, 1.2-1.4x the tiled kernel - it is kept and
-            # the keys stay plain: both forms are exact to their one rounding, the attention kernels take either.  ADVICE r5)
+            # (pre-scaled keys on the per-GEMM path go through st_gemm's column-range epilogue.  Where the weight-stationary
+            # st_gemm_ws would serve the projection - width 256, encoder-sized row counts, 1.2-1.4x the tiled kernel - the keys
+            # stay plain UNLESS a gradient is wanted and the streams can serve the backward: 64-wide heads, more than 128
+            # rows.  Both key forms are exact to their one rounding in the forward and in the general backward kernels, but
+            # the streams are accurate on pre-scaled keys only and st_attn_bwd no longer sends them plain ones; giving up
+            # st_gemm_ws for the streams is the cheaper of the two - LABNOTES.md, "Plain keys no longer reach the backward
+            # streams".  ADVICE r5)
+            streams = any(ctx.needs_input_grad) and d // H == 64 and min(q_rows.max_len, k_rows.max_len) > 128
             kpre = (x_kv is None and not causal and MhaFn.PRESCALE_KEYS
-                    and not nv.ws_ok(x_q.shape[0], 3 * s.d_model, x_q.shape[1]))
+                    and (streams or not nv.ws_ok(x_q.shape[0], 3 * s.d_model, x_q.shape[1])))
             qkv, kvbuf, attn_ctx, ores, lse, out, xhat, rstd = MhaFn.compute(
                 x_q, x_kv, s, q_rows, k_rows, causal, drop, kv_acc, any(ctx.needs_input_grad), scale, kpre)
         if AttnTap.active is not None:

@@ -360,9 +360,10 @@ def test_attention_fwd_bwd(case):
 
 
 # delta supplied by the producer of dO (O = None): ONE launch for dQ and dK/dV - the form the training step uses.  Long non-causal
-# problems with 64-wide heads take the hand-scheduled streams of csrc/st_attn_bwd64.hip (tile counts 1..16, utterances whose last
-# 64-row tile holds 1 / 31 / 32 / 33 / 63 / 64 rows, a batch whose last 128-row tile has idle waves, padded layout); the others
-# (causal, 32-wide heads, few queries) the general kernels' merged launch.
+# problems with 64-wide heads and PRE-SCALED keys take the hand-scheduled streams of csrc/st_attn_bwd64.hip (tile counts 1..16,
+# utterances whose last 64-row tile holds 1 / 31 / 32 / 33 / 63 / 64 rows, a batch whose last 128-row tile has idle waves, padded
+# layout); the others (plain keys, causal, 32-wide heads, few queries) the general kernels' merged launch.  The stream-shaped rows
+# run both ways: the plain call and its pre-scaled twin (_streams_shape).
 DELTA_CASES = [
     (3, 4, 64, None, [200, 131, 64], False, True),
     (3, 4, 64, None, [129, 130, 257], False, True),
@@ -379,6 +380,11 @@ DELTA_CASES = [
     (3, 2, 128, [64, 1, 40], [700, 256, 65], False, True),
     (3, 4, 32, [33, 64, 2], [513, 300, 256], False, False),
 ]
+
+
+def _streams_shape(case, c):
+    """st_attn_bwd's one-launch form sends this shape to the streams of csrc/st_attn_bwd64.hip when the keys are pre-scaled."""
+    return case[2] == 64 and not case[5] and min(c["max_q"], c["max_k"]) > 128
 
 
 def test_attention_backward_key_split_across_workgroups_is_reproducible():
@@ -552,6 +558,20 @@ def test_attention_bwd_delta_supplied(case, use_work):
                 c["max_k"], c["causal"], c["scale"], work_q=wq, work_k=wk)
     for g_, r_, nm, tol in zip(got, ref, ("dQ", "dK", "dV"), (2.5e-2, 2.5e-2, 2e-2)):      # utterance rows (padded layout: the rest is untouched)
         check_attn(gd[nm], g_, r_, c, nm, tol, L_ATTN[nm], "attention (delta supplied) %s %s" % (case, nm))
+    if not _streams_shape(case, c):
+        return
+    # the pre-scaled twin - the streams: K~ to the kernel, k_prescaled = True to the emulation (lse and delta from ITS forward on K~)
+    kt = (c["K"].float() * (c["scale"] * nv.K_LOG2_SCALE)).to(BF16)
+    em.attn_fwd(c["Q"], kt, c["V"], O, lse, *meta_c, H, c["max_q"], c["causal"], c["scale"], max_k=c["max_k"], k_prescaled=True)
+    delta = (c["dO"].float() * O.float()).view(Mq, H, dk).sum(-1).t().contiguous().view(-1)
+    em.attn_bwd(c["Q"], kt, c["V"], None, c["dO"], lse, delta, *ref, *meta_c, H, c["max_q"], c["max_k"], c["causal"], c["scale"],
+                k_prescaled=True)
+    gd = _attn_guards(c)
+    got = [gd[n].view for n in ("dQ", "dK", "dV")]
+    nv.attn_bwd(cu(c["Q"]), cu(kt), cu(c["V"]), None, cu(c["dO"]), cu(lse), cu(delta), *got, *[cu(m) for m in meta_c], H, c["max_q"],
+                c["max_k"], c["causal"], c["scale"], work_q=wq, work_k=wk, k_prescaled=True)
+    for g_, r_, nm, tol in zip(got, ref, ("dQ", "dK", "dV"), (2.5e-2, 2.5e-2, 2e-2)):
+        check_attn(gd[nm], g_, r_, c, nm, tol, L_ATTN[nm], "attention (delta supplied, pre-scaled keys: the streams) %s %s" % (case, nm))
 
 
 # Pre-scaled keys (round 5): K~ = bf16(scale * log2(e) * k), scaled in the fp32 epilogue of the projection that produced the keys
@@ -1108,15 +1128,22 @@ def test_gemm_dgrad_with_delta_epilogue(M, N, K, hd):
                                   (2, 2, 128, [50, 33], [700, 517], False, True)])
 def test_attention_backward_single_launch(case):
     """O = None: delta comes in precomputed and dQ + dK/dV run as one launch - identical results to the two-kernel path
-    where the general kernels serve both; long non-causal problems with 64-wide heads take the hand-scheduled streams of
-    csrc/st_attn_bwd64.hip in the one-launch form (K or Q pre-multiplied by scale * log2 e and rounded to bf16 once more:
-    the same mathematics within a bf16 rounding of the scores, not bit-identical)."""
+    where the general kernels serve both (plain keys at every shape); long non-causal problems with 64-wide heads and PRE-SCALED
+    keys take the hand-scheduled streams of csrc/st_attn_bwd64.hip in the one-launch form (another schedule and summation order:
+    the same mathematics, not bit-identical) - those shapes run both ways."""
     c = _attn_case(*case, seed=31)
-    Q, K, V, dO = cu(c["Q"]), cu(c["K"]), cu(c["V"]), cu(c["dO"])
+    _single_launch(case, c, False)
+    if _streams_shape(case, c):
+        _single_launch(case, c, True)
+
+
+def _single_launch(case, c, prescaled):
+    Q, V, dO = cu(c["Q"]), cu(c["V"]), cu(c["dO"])
+    K = cu((c["K"].float() * (c["scale"] * nv.K_LOG2_SCALE)).to(BF16) if prescaled else c["K"])
     meta = [cu(c[k]) for k in ("q_off", "q_len", "k_off", "k_len")]
     O = torch.zeros(c["Mq"], c["d"], dtype=BF16, device="cuda")
     lse = torch.zeros(c["H"] * c["Mq"], dtype=F32, device="cuda")
-    nv.attn_fwd(Q, K, V, O, lse, *meta, c["H"], c["max_q"], c["causal"], c["scale"], max_k=c["max_k"])
+    nv.attn_fwd(Q, K, V, O, lse, *meta, c["H"], c["max_q"], c["causal"], c["scale"], max_k=c["max_k"], k_prescaled=prescaled)
     outs = []
     for single in (False, True):
         delta = torch.zeros_like(lse)
@@ -1130,10 +1157,10 @@ def test_attention_backward_single_launch(case):
             gdd = GV(c["H"] * c["Mq"])
             delta = gdd.view
         nv.attn_bwd(Q, K, V, None if single else O, dO, lse, delta, dQ, dK, dV, *meta, c["H"], c["max_q"], c["max_k"],
-                    c["causal"], c["scale"])
+                    c["causal"], c["scale"], k_prescaled=prescaled)
         outs.append((dQ, dK, dV, delta))
     check_attn(gdd, outs[0][3], _delta_of(dO, O, c["H"]), c, "delta", 1e-5, L_ATTN["delta"], "two-kernel backward: delta")
-    streams = case[2] == 64 and not case[5] and min(c["max_q"], c["max_k"]) > 128
+    streams = prescaled and _streams_shape(case, c)
     # (few queries against many keys: the one-launch form cuts the dQ items' keys over workgroups - other fp32 partial sums, round 6)
     split = nv.load()._cdll.st_attn_bwd_split_kib(case[0], c["H"], case[2], c["max_q"], c["max_k"], int(case[5])) > 0
     for a, b, nm in zip(outs[0][:3], outs[1][:3], ("dQ", "dK", "dV")):
@@ -1153,7 +1180,8 @@ def test_attention_backward_streams_with_dropout(lens, p, monkeypatch):
     *_drop.inc) regenerates the forward's keep decisions inside the instruction stream (SDWA byte compares on the lowbias32
     words of st_attn_common.cuh keep16, one DPP exchange per 2 x 2 block pair).  Against the general kernels with the SAME
     Drop (ST_ATTN_BWD64=e keeps the streams for eval mode only): a single wrong keep decision is an O(1 / sqrt(n)) error, the
-    two agree to the bf16 rounding of the pre-scaled operand (measured 2.8e-3)."""
+    two agree within 6e-3.  The streams serve PRE-SCALED keys only: K~ reaches them; the plain call beside it takes the general
+    kernels under either setting of the switch - bit for bit the same."""
     from st_amd.functional import Rows, attn_work
     H, dk = 4, 64
     d, scale = H * dk, 1 / math.sqrt(dk)
@@ -1169,29 +1197,38 @@ def test_attention_backward_streams_with_dropout(lens, p, monkeypatch):
     drop = nv.Drop(torch.tensor([4321], dtype=torch.int32, device="cuda"), 55, p)
     O = torch.empty(M, d, dtype=BF16, device="cuda")
     lse = torch.empty(H * M, dtype=F32, device="cuda")
-    nv.attn_fwd(Q, K, V, O, lse, q_off, q_len, q_off, q_len, H, max(lens), False, scale, work=wf, max_k=max(lens), drop=drop)
-    delta = (dO.float() * O.float()).view(M, H, dk).sum(-1).t().contiguous().view(-1)
-    outs = {}
-    for mode in ("e", "1"):
-        monkeypatch.setenv("ST_ATTN_BWD64", mode)
-        nv.env_refresh()          # (the library caches its development switches)
-        gds = [GO(M, d) for _ in range(3)]
-        got = [gd.view for gd in gds]
-        nv.attn_bwd(Q, K, V, None, dO, lse, delta, *got, q_off, q_len, q_off, q_len, H, max(lens), max(lens), False, scale,
-                    work_q=wq, work_k=wk, drop=drop)
-        torch.cuda.synchronize()
-        for gd, nm in zip(gds, ("dQ", "dK", "dV")):
-            gd.assert_intact("backward streams with dropout p = %s, ST_ATTN_BWD64=%s: %s" % (p, mode, nm))
-        outs[mode] = got
-    for a, b, nm in zip(outs["e"], outs["1"], ("dQ", "dK", "dV")):
-        assert torch.isfinite(b.float()).all(), nm
-        check(b, a, 6e-3, "backward streams with dropout p = %s: %s" % (p, nm), tol_local=L_ATTN_DROP[nm])
-    # and the masks matter: without them the result is far away (guards against a variant that silently ignores the Drop)
-    monkeypatch.delenv("ST_ATTN_BWD64")
-    nv.env_refresh()
-    plain = [torch.zeros(M, d, dtype=BF16, device="cuda") for _ in range(3)]
-    nv.attn_bwd(Q, K, V, None, dO, lse, delta, *plain, q_off, q_len, q_off, q_len, H, max(lens), max(lens), False, scale, work_q=wq, work_k=wk)
-    assert float((plain[2].float() - outs["1"][2].float()).norm() / outs["1"][2].float().norm()) > 0.1
+    Kplain, streams_shape = K, max(lens) > 128
+    for prescaled in (False, True):
+        K = (Kplain.float() * (scale * nv.K_LOG2_SCALE)).to(BF16) if prescaled else Kplain
+        nv.attn_fwd(Q, K, V, O, lse, q_off, q_len, q_off, q_len, H, max(lens), False, scale, work=wf, max_k=max(lens), drop=drop,
+                    k_prescaled=prescaled)
+        delta = (dO.float() * O.float()).view(M, H, dk).sum(-1).t().contiguous().view(-1)
+        outs = {}
+        for mode in ("e", "1"):
+            monkeypatch.setenv("ST_ATTN_BWD64", mode)
+            nv.env_refresh()          # (the library caches its development switches)
+            gds = [GO(M, d) for _ in range(3)]
+            got = [gd.view for gd in gds]
+            nv.attn_bwd(Q, K, V, None, dO, lse, delta, *got, q_off, q_len, q_off, q_len, H, max(lens), max(lens), False, scale,
+                        work_q=wq, work_k=wk, drop=drop, k_prescaled=prescaled)
+            torch.cuda.synchronize()
+            for gd, nm in zip(gds, ("dQ", "dK", "dV")):
+                gd.assert_intact("backward streams with dropout p = %s, ST_ATTN_BWD64=%s, prescaled=%s: %s" % (p, mode, prescaled, nm))
+            outs[mode] = got
+        for a, b, nm in zip(outs["e"], outs["1"], ("dQ", "dK", "dV")):
+            assert torch.isfinite(b.float()).all(), nm
+            if prescaled:
+                check(b, a, 6e-3, "backward streams with dropout p = %s: %s" % (p, nm), tol_local=L_ATTN_DROP[nm])
+                assert not streams_shape or not same_bits(a, b), "pre-scaled keys did not reach the streams' dropout variant: %s" % nm
+            else:
+                assert same_bits(a, b), "plain keys with dropout did not take the general kernels under ST_ATTN_BWD64=1: %s" % nm
+        # and the masks matter: without them the result is far away (guards against a variant that silently ignores the Drop)
+        monkeypatch.delenv("ST_ATTN_BWD64")
+        nv.env_refresh()
+        plain = [torch.zeros(M, d, dtype=BF16, device="cuda") for _ in range(3)]
+        nv.attn_bwd(Q, K, V, None, dO, lse, delta, *plain, q_off, q_len, q_off, q_len, H, max(lens), max(lens), False, scale, work_q=wq,
+                    work_k=wk, k_prescaled=prescaled)
+        assert float((plain[2].float() - outs["1"][2].float()).norm() / outs["1"][2].float().norm()) > 0.1
 
 
 @pytest.mark.parametrize("M,N,K,with_aux,p", [(300, 128, 128, True, 0), (1000, 256, 1024, True, 0), (130, 256, 768, False, 0),

@@ -1,7 +1,8 @@
 """Where the local bounds of tests/test_kernels_gpu.py come from (tests/LOCAL_BOUNDS.md): on the CPU, every emulation of
 tests/_emul.py evaluated with fp32 and with fp64 accumulation - same bf16 rounding points - over the kernel tests' own cases;
 the largest per-row / per-column / per-element ratio of tests/_local.py per family and output; likewise the slow-path attention
-kernels over the cases of tests/test_slow_attention_gpu.py (families "dense" and "probs").  No kernel runs here.
+kernels over the cases of tests/test_slow_attention_gpu.py (families "dense" and "probs") and the fast attention kernels at sharp
+scores over the cases of tests/test_sharp_attention_gpu.py (family "sharp").  No kernel runs here.
 
     python tools/local_bounds.py            # prints one line per family / output
 """
@@ -18,6 +19,7 @@ for p in (ROOT, os.path.join(ROOT, "speech-tranformer-pytorch_amd")):
 
 from st_amd import chains, native as nv          # noqa: E402
 from tests import _emul as em                     # noqa: E402
+from tests import _sharp_attn as sh               # noqa: E402
 from tests import _slow_attn as sa                # noqa: E402
 from tests import test_kernels_gpu as tk          # noqa: E402
 from tests._local import local_figures            # noqa: E402
@@ -205,6 +207,30 @@ def dense():
                 note("dense (bf16 vs fp64)", nm, res[F32][nm], c.ref[nm])
 
 
+def sharp():
+    """The fast attention kernels over the cases of tests/test_sharp_attention_gpu.py (tests/_sharp_attn.py): the rule - the emulation
+    in fp32 against fp64, same rounding points - per output, and "(bf16 vs fp64)": the fp32 emulation against the UNROUNDED fp64
+    reference the test compares with, row by row - the room the kernels' own rounding points take of the bound in force."""
+    for _, kw in sh.cases():
+        c = sh.build(**kw)
+        out = {be: sh.outputs(c, sh.launch(c, be)) for be in (sh.CPU, sh.CPU64)}
+        fam = "sharp, dropout" if c.p > 0 else "sharp"
+        for nm in out[sh.CPU]:
+            if nm == "Ores":
+                continue
+            rows = c.rows[sh.side(nm)]
+            a, b = out[sh.CPU][nm], out[sh.CPU64][nm]
+            if nm == "delta":          # a function of the backward's inputs: the fp32 sum against the fp64 one over the same O
+                b = c.delta_of_O
+            note(fam, nm, a, b, rows=rows)
+            if nm in c.ref and nm not in ("lse", "delta"):
+                note(fam + " (bf16 vs fp64)", nm, a, c.ref[nm], rows=rows)
+            elif nm == "O+Ores":
+                note(fam + " (bf16 vs fp64)", nm, a, c.ref["O"], rows=rows)
+            elif nm == "lse":
+                note(fam + " (bf16 vs fp64)", nm, a, c.ref[nm].float(), rows=rows)
+
+
 def probs():
     """st_attn_probs over the cases of tests/test_slow_attention_gpu.py: the emulation's fp32 maps against the fp64 reference."""
     for kw in sa.probs_cases():
@@ -258,6 +284,7 @@ if __name__ == "__main__":
     probs_and_ctc()
     dense()
     probs()
+    sharp()
     losses()
     for (family, name, axis), v in sorted(worst.items()):
         print("%-28s %-8s %-8s worst ratio %.3e   x3 = %.3e" % (family, name, axis, v, 3 * v))
