@@ -31,7 +31,7 @@ extern "C" {
 typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C: no HIP header needed */
 
 /* Library ABI version, bumped on any signature change (2: round 5's k_prescaled / dense attention / grad_scale arguments;
- * 3, 4: round 6 - 4 added the column-sum workspace of st_row_chain_bwd; 5: the joint CTC / attention beam search; 6: st_ctc_loss_*).  A host binding must refuse a library whose st_version() differs from the header it was written against:
+ * 3, 4: round 6 - 4 added the column-sum workspace of st_row_chain_bwd; 5: the joint CTC / attention beam search; 6: st_ctc_loss_*; 7: st_row_chain512_bwd removed).  A host binding must refuse a library whose st_version() differs from the header it was written against:
  * through ctypes / dlsym a stale libst_hip.so would be called with shifted arguments.
  * This header is the ONLY copy of the ABI: every source under csrc/ is compiled against it (csrc/st_common.cuh includes it, so a
  * definition that disagrees with its declaration stops the build), st_version() returns this macro, and st_amd/native.py
@@ -39,7 +39,7 @@ typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C:
  * it here (parameter types: pointers, st_stream_t, int, unsigned, float, long, long long - the binding refuses anything
  * else), define it in csrc/, write its wrapper in st_amd/native.py - and bump the number if an existing signature moved.
  * (Entry points added since version 6 go into the extension section at the end of this file, which says why.) */
-#define ST_ABI_VERSION 6
+#define ST_ABI_VERSION 7
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -222,17 +222,6 @@ int st_row_chain512(st_stream_t stream, int M, const void* wfrag, int n_blocks, 
                     unsigned drop1_salt, int drop1_thresh, float drop1_scale, unsigned drop2_salt, int drop2_thresh,
                     float drop2_scale, int post_blocks, const float* bp, void* P, int ldp, float post_kscale);
 int st_row_chain512_mask_words(int M, int d_ff);
-/* ... and its backward (csrc/st_rowchain_pipe512_bwd.cuh; arguments as st_row_chain_bwd with 512-wide row matrices, HEAD + FFN +
- * TAIL all required; head_blocks 0 or 6; 8 heads of 64 columns: delta [8, M]).  The stream holds the TRANSPOSED blocks in the order
- *   (h, u) -> 6 h + u of Wp [1536, 512]  |  per hidden chunk c: W2^T (j = 0, 1), W1^T (h = 0, 1)  |  Wo^T (h, j) -> 2 h + j
- * (st_amd.chains.encoder512_blocks_bwd).  n_blocks = 2 head_blocks + 4 d_ff / 256 + 4. */
-int st_row_chain512_bwd(st_stream_t stream, int M, const void* wfrag, int n_blocks, int next_blocks, int head_blocks, const void* dP,
-                        int ldp, const void* G, int ldg, const void* xhat_a, const float* rstd_a, const float* gamma_a,
-                        const unsigned* drop_seed, unsigned drop_salt, int drop_thresh, float drop_scale, void* ds_a,
-                        float* dgamma_a, float* dbeta_a, float* dbias_a, int d_ff, const unsigned long long* relu_bits,
-                        float mask_scale, void* dH, const void* xhat_b, const float* rstd_b, const float* gamma_b, void* ds_b,
-                        float* dgamma_b, float* dbeta_b, float* dbias_b, const void* O, const void* Ores, int ldo, void* dctx,
-                        int lddc, float* delta);
 
 /* relu_bits (st_row_chain: optional output, st_row_chain_bwd: input): which hidden values of the feed-forward sublayer are
  * > 0 after ReLU and dropout (the mask of SubLayers.py:25's backward), one bit per value in a layout private to the two

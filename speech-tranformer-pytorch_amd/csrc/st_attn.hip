@@ -587,8 +587,7 @@ bool key_split(int max_q, int max_k, int causal) { return !causal && max_q <= 64
 // XS_TICKETS tickets (zero before the first launch; the kernel leaves them zero), then xs fp32 partials of 64 x d_k per item.
 constexpr int XS_TICKETS = 4096;
 int xsplit_for(int d_k, int max_q, int max_k, int causal) {
-  static const bool off = [] { const char* e = getenv("ST_ATTN_XSPLIT"); return e && e[0] == '0'; }();      // development switch
-  if (off || !key_split(max_q, max_k, causal)) return 1;
+  if (!key_split(max_q, max_k, causal)) return 1;
   const int nt = (max_k + 127) / 128;
   return nt < 4 ? nt : 4;
 }
@@ -610,12 +609,6 @@ int plan(AttnArgs& a, const int* work, int n_work, int B, int H, int max_rows, i
   return (work ? n_work : B * a.tiles_max) * H;
 }
 
-// development switch (ST_ATTN_IMPL=1: the general kernels everywhere), read once
-int attn_impl() {
-  static const int v = [] { const char* e = getenv("ST_ATTN_IMPL"); return e ? atoi(e) : 0; }();
-  return v;
-}
-
 // development switches (same-process A/B runs of the specialised kernels against the general ones): read from the
 // environment ONCE, and again only when a host asks (st_env_refresh: tests and tools/dev call it after changing a variable) -
 // the production dispatch never calls getenv
@@ -635,7 +628,7 @@ AttnEnv& attn_env() {
 
 // long non-causal problems with 64-wide heads take the plain-exponential forward of st_attn64.hip
 bool fwd_long64(int d_k, int max_q, int max_k, int causal) {
-  return d_k == 64 && !causal && max_q > 128 && attn_impl() != 1 && !attn_env().fwd64_off;
+  return d_k == 64 && !causal && max_q > 128 && !attn_env().fwd64_off;
 }
 
 // ... and the hand-scheduled backward of st_attn_bwd64.hip (delta supplied by the producer of dO).  ST_ATTN_BWD64=0 keeps the
@@ -644,14 +637,14 @@ bool fwd_long64(int d_k, int max_q, int max_k, int causal) {
 // body, Q in the dK/dV body: a different perturbation of every score in each), 1.9-4x the general kernels' error at the scores
 // of a trained model (profiles/attn_sharp_accuracy_before.txt); the general kernels scale the fp32 score and take plain keys instead
 bool bwd_long64(int d_k, int max_q, int max_k, int causal, bool drop, int k_prescaled) {
-  if (!(k_prescaled && d_k == 64 && !causal && max_q > 128 && max_k > 128 && attn_impl() != 1)) return false;
+  if (!(k_prescaled && d_k == 64 && !causal && max_q > 128 && max_k > 128)) return false;
   const int mode = attn_env().bwd64;
   return mode == 0 || (mode == 2 && !drop);
 }
 
 // few queries against many keys with 64-wide heads (the decoder-encoder attention) take the forward of st_attn_xs.hip
 bool fwd_xs(int d_k, int max_q, int max_k, int causal) {
-  return d_k == 64 && key_split(max_q, max_k, causal) && attn_impl() != 1 && !attn_env().xs_off;
+  return d_k == 64 && key_split(max_q, max_k, causal) && !attn_env().xs_off;
 }
 
 }  // namespace

@@ -13,7 +13,6 @@
 // the lane): LayerNorm's row statistics are an in-lane sum, one exchange with lane ^ 32 and (N > 128) one
 // LDS round between the waves that share a row.  Values leave through an LDS patch as 256-byte row segments.
 #include "st_common.cuh"
-#include <cstdlib>
 
 #ifndef ST_GEMM_SC1
 #define ST_GEMM_SC1 0      // development: bf16 output rows write-through (store16_wt)
@@ -382,8 +381,7 @@ extern "C" int st_gemm_ln(hipStream_t stream, const void* X, int ldx, const void
     // (round 3) 128-row tiles on 8 waves for encoder-sized M and long contractions (two row blocks per wave, see Geo): BM = 32
     // re-staged the whole weight matrix for every 32 rows (752 workgroups x 0.5-1 MB at config 3), BM = 64 still asked more of
     // the vector-memory path than it delivers (M = 24060, K = 2048: 117 -> 96 us)
-    static const bool mb1 = getenv("ST_GEMM_LN_MB1") != nullptr;      // development: the 64-row tiles
-    if (mb1 || K < 1024) {      // short contractions are epilogue-bound: 47.4 us (64 rows) vs 48.8 (128) at K = 512
+    if (K < 1024) {      // short contractions are epilogue-bound: 47.4 us (64 rows) vs 48.8 (128) at K = 512
       const dim3 grid((M + 63) / 64), blk(512);
       if (a.drop_where == 1) hipLaunchKernelGGL((gemm_ln_kernel<512, 1, 1, true>), grid, blk, 0, stream, a);
       else if (a.drop_where == 2) hipLaunchKernelGGL((gemm_ln_kernel<512, 2, 1, true>), grid, blk, 0, stream, a);

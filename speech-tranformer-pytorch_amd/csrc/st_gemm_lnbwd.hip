@@ -19,7 +19,6 @@
 // the column sums of dy / dy*xhat are taken in the coalesced layout (8 columns per thread); pass 2 forms dx, which
 // leaves as 256-byte row segments while its column sum is taken.
 #include "st_common.cuh"
-#include <cstdlib>
 
 #ifndef ST_GEMM_SC1
 #define ST_GEMM_SC1 0      // development: bf16 output rows write-through (store16_wt)
@@ -415,8 +414,7 @@ extern "C" int st_gemm_lnbwd(hipStream_t stream, const void* dY, int lddy, const
     return 0;
   }
   if (N == 512 && M > 64 * 128) {      // (round 3) d_model 512, encoder-sized M: 8 waves, as in st_gemm_ln.hip
-    static const bool mb1 = getenv("ST_GEMM_LN_MB1") != nullptr;      // development: the 64-row tiles everywhere
-    if (mb1 || Kc < 1024) {            // 64-row tiles
+    if (Kc < 1024) {                   // 64-row tiles
       const dim3 grid((M + 63) / 64);
       if (drop) hipLaunchKernelGGL((gemm_lnbwd_kernel<512, true, true>), grid, dim3(512), 0, stream, a);
       else hipLaunchKernelGGL((gemm_lnbwd_kernel<512, false, true>), grid, dim3(512), 0, stream, a);

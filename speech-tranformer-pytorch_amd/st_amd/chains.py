@@ -96,20 +96,6 @@ def encoder512_blocks(wo: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, wp=N
     return out
 
 
-def encoder512_blocks_bwd(wo: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, wp=None):
-    """The block order of st_row_chain512_bwd, all read transposed: Wp [1536, 512] as (h, u) -> 6 h + u (contraction over the
-    weight's rows 256 u .., output = its columns 256 h ..); per hidden chunk c: W2^T (j = 0, 1: rows 256 j .. of W2, columns c),
-    W1^T (h = 0, 1: rows c of W1, columns 256 h ..); Wo^T as (h, j) -> 2 h + j (rows 256 j .., columns 256 h ..)."""
-    d_ff = w1.shape[0]
-    out = []
-    if wp is not None:
-        out += [(wp, u * BLK, h * BLK, True) for h in range(2) for u in range(6)]
-    for c in range(0, d_ff, BLK):
-        out += [(w2, 0, c, True), (w2, BLK, c, True), (w1, c, 0, True), (w1, c, BLK, True)]
-    out += [(wo, j * BLK, h * BLK, True) for h in range(2) for j in range(2)]
-    return out
-
-
 class ChainSet:
     def __init__(self, device):
         self.device = torch.device(device)
@@ -327,21 +313,11 @@ class EncoderChains:
             self.set.finalize()
             self.q0 = None
             self.e = [self.set.chain(c, True) for c in ids]
-            # backward chains in running order (last layer first): [next layer's q|k|v projection] + feed-forward + output_linear
-            self.bset = ChainSet(arena.device)
-            bids = {}
-            for l in range(n - 1, -1, -1):
-                sa, ff = layers[l].slf_attn._st, layers[l].pos_ffn._st
-                bids[l] = self.bset.add(encoder512_blocks_bwd(sa.w_o, ff.w1, ff.w2, layers[l + 1].slf_attn._st.w_qkv if l + 1 < n else None))
-            self.bset.finalize()
-            self.bwd = [self.bset.chain(bids[l], True) for l in range(n)]
-            # The backward chain (st_row_chain512_bwd) is built and tested but OFF by default: at config 3 it measured 253 us per
-            # launch against 216 for the per-GEMM kernels it replaces (gemm_lnbwd + dgrad GEMMs: 11.57 vs 11.12 ms per step, same
-            # box, round 6) - 64-row workgroups run two rounds on 256 CUs and the LayerNorm backward's column sums cost what the
-            # separate kernels' do.  ST_CHAIN512=1 turns it on, =0 turns the forward chains off as well.
-            self.use_bwd = sa.n_head * 64 == self.d and os.environ.get("ST_CHAIN512", "f") == "1"
+            # no backward chain at this width: the per-GEMM kernels (gemm_lnbwd + dgrad GEMMs) measured faster than one launch of
+            # 64-row workgroups, which runs two rounds on 256 CUs (216 vs 253 us per layer at config 3, round 6)
+            self.use_bwd, self.bwd = False, None
             self.layer_hook = None
-            ChainHub.of(arena).add(self.set, self.bset)
+            ChainHub.of(arena).add(self.set)
             return
         # layer 0's q | k | v projection: a chain of its own (three blocks, no PRE / FFN) - every encoder layer's keys leave
         # their projection PRE-SCALED by scale * log2(e) in the chain's fp32 epilogue (st_row_chain's post_kscale), so that no
@@ -354,27 +330,31 @@ class EncoderChains:
         self.set.finalize()
         self.q0 = self.set.chain(q0, False)
         self.e = [self.set.chain(c, True) for c in ids]
-        # backward chains, stored in running order (last layer first): [next layer's q|k|v projection] + feed-forward +
-        # output_linear, all read transposed
-        self.bset = ChainSet(arena.device)
-        ids = {}
-        for l in range(n - 1, -1, -1):
-            sa, ff = layers[l].slf_attn._st, layers[l].pos_ffn._st
-            head = t_blocks(blocks_of(layers[l + 1].slf_attn._st.w_qkv)) if l + 1 < n else []
-            ids[l] = self.bset.add(head + ffn_blocks_bwd(ff.w1, ff.w2) + t_blocks(blocks_of(sa.w_o)))
-        self.bset.finalize()
-        self.bwd = [self.bset.chain(ids[l], True) for l in range(n)]
+        self.use_bwd = layers[0].slf_attn._st.n_head * 64 == BLK        # the delta epilogue's heads are 64 columns
+        self.bwd = None
+        sets = [self.set]
+        if self.use_bwd:
+            # backward chains, stored in running order (last layer first): [next layer's q|k|v projection] + feed-forward +
+            # output_linear, all read transposed
+            bset = ChainSet(arena.device)
+            ids = {}
+            for l in range(n - 1, -1, -1):
+                sa, ff = layers[l].slf_attn._st, layers[l].pos_ffn._st
+                head = t_blocks(blocks_of(layers[l + 1].slf_attn._st.w_qkv)) if l + 1 < n else []
+                ids[l] = bset.add(head + ffn_blocks_bwd(ff.w1, ff.w2) + t_blocks(blocks_of(sa.w_o)))
+            bset.finalize()
+            self.bwd = [bset.chain(ids[l], True) for l in range(n)]
+            sets.append(bset)
         # (no split_work for the encoder's chains: cutting the hidden dimension over workgroups changes the fp32 summation order
         # per row, and WHICH split a launch takes depends on its row count - an utterance's activations would then depend on what
         # else is in the batch / on the data-parallel shard size.  Measured: a 4-utterance shard 1.667 -> 1.650 ms with a two-way
         # split, tests/test_modules_gpu.py::test_full_size_batch_split_invariance 5e-3 -> 1.6e-2.  Not worth it.  LABNOTES round 5.)
         if os.environ.get("ST_CHAIN_SPLIT", "1") == "e":      # (development switch: the measurement above)
             work = torch.zeros(nv.split_work_words(), dtype=torch.int32, device=arena.device)
-            for ch in self.e + self.bwd:
+            for ch in self.e + (self.bwd or []):
                 ch.split_work = work
-        self.use_bwd = sa.n_head * 64 == BLK        # the delta epilogue's heads are 64 columns
         self.layer_hook = None      # optional callable(first_finished_layer): EncoderBackward.input_grad / trainer.TrainStep
-        ChainHub.of(arena).add(self.set, self.bset)
+        ChainHub.of(arena).add(*sets)
 
     @staticmethod
     def plan(layers, arena):
@@ -385,8 +365,6 @@ class EncoderChains:
             if any(getattr(m, "_st_arena", None) is not arena for m in (sa, ff)):
                 return None
             if sa._st.d_model not in (BLK, 512) or ff._st.d_ff % BLK:
-                return None
-            if sa._st.d_model == 512 and os.environ.get("ST_CHAIN512", "f") == "0":      # (development switch: the per-GEMM path)
                 return None
         return EncoderChains(layers, arena)
 
@@ -468,24 +446,28 @@ class DecoderChains:
             work = torch.zeros(nv.split_work_words(), dtype=torch.int32, device=self.f2[0].stream.device)
             for ch in self.f2:
                 ch.split_work = work
-        # backward chains in running order (last layer first): B2(l) = [q|k|v projection of layer l + 1] + feed-forward +
-        # the encoder-decoder attention's output_linear; B1(l) = its q projection + the self-attention's output_linear
-        self.bset = ChainSet(arena.device)
-        b1, b2 = {}, {}
-        for l in range(n - 1, -1, -1):
-            sa, ca, ff = layers[l].slf_attn._st, layers[l].enc_attn._st, layers[l].pos_ffn._st
-            head = t_blocks(blocks_of(layers[l + 1].slf_attn._st.w_qkv)) if l + 1 < n else []
-            b2[l] = self.bset.add(head + ffn_blocks_bwd(ff.w1, ff.w2) + t_blocks(blocks_of(ca.w_o)))
-            b1[l] = self.bset.add(t_blocks(blocks_of(ca.w_q)) + t_blocks(blocks_of(sa.w_o)))
-        self.bset.finalize()
-        self.bwd2 = [self.bset.chain(b2[l], True) for l in range(n)]
-        if self.f2 and self.f2[0].split_work is not None and os.environ.get("ST_CHAIN_SPLIT", "1") != "f":      # ("f": forward only)
-            for ch in self.bwd2:
-                ch.split_work = self.f2[0].split_work       # (forward and backward launches are ordered on one stream)
-        self.bwd1 = [self.bset.chain(b1[l], True) for l in range(n)]
-        self.use_bwd = sa.n_head * 64 == BLK        # the delta epilogue's heads are 64 columns
+        self.use_bwd = layers[0].slf_attn._st.n_head * 64 == BLK        # the delta epilogue's heads are 64 columns
+        self.bwd1 = self.bwd2 = None
+        sets = [self.set]
+        if self.use_bwd:
+            # backward chains in running order (last layer first): B2(l) = [q|k|v projection of layer l + 1] + feed-forward +
+            # the encoder-decoder attention's output_linear; B1(l) = its q projection + the self-attention's output_linear
+            bset = ChainSet(arena.device)
+            b1, b2 = {}, {}
+            for l in range(n - 1, -1, -1):
+                sa, ca, ff = layers[l].slf_attn._st, layers[l].enc_attn._st, layers[l].pos_ffn._st
+                head = t_blocks(blocks_of(layers[l + 1].slf_attn._st.w_qkv)) if l + 1 < n else []
+                b2[l] = bset.add(head + ffn_blocks_bwd(ff.w1, ff.w2) + t_blocks(blocks_of(ca.w_o)))
+                b1[l] = bset.add(t_blocks(blocks_of(ca.w_q)) + t_blocks(blocks_of(sa.w_o)))
+            bset.finalize()
+            self.bwd2 = [bset.chain(b2[l], True) for l in range(n)]
+            if self.f2 and self.f2[0].split_work is not None and os.environ.get("ST_CHAIN_SPLIT", "1") != "f":      # ("f": forward only)
+                for ch in self.bwd2:
+                    ch.split_work = self.f2[0].split_work       # (forward and backward launches are ordered on one stream)
+            self.bwd1 = [bset.chain(b1[l], True) for l in range(n)]
+            sets.append(bset)
         self.layer_hook = None      # optional callable(first_finished_layer): EncoderBackward.input_grad / trainer.TrainStep
-        ChainHub.of(arena).add(self.set, self.bset)
+        ChainHub.of(arena).add(*sets)
 
     @staticmethod
     def plan(layers, arena):

@@ -18,7 +18,6 @@ from __future__ import annotations
 
 import collections
 import math
-import os
 from typing import Optional
 
 import torch
@@ -243,7 +242,7 @@ def attn_work(q_rows: Rows, k_rows: Rows, causal: bool, d_k: int = 64, n_head: i
 def _work_lists(q_rows, k_rows, causal, d_k, n_head, lq, lk, xcd_groups=True):
     """The three lists of attn_work as Python lists, for the utterance lengths lq / lk."""
     rows = [nv.attn_tile_rows(w, d_k, q_rows.max_len, k_rows.max_len, causal) for w in range(3)]
-    ng = 8 // n_head if xcd_groups and n_head in (1, 2, 4, 8) and not os.environ.get("ST_NO_XCD_AFFINITY") else 1
+    ng = 8 // n_head if xcd_groups and n_head in (1, 2, 4, 8) else 1
     # deal the utterances into ng groups of equal total cost (longest first onto the lightest group)
     group, load = [0] * q_rows.B, [0.0] * ng
     if ng > 1:
@@ -316,8 +315,8 @@ class _Deferred:
     HIP graph.  The operand tensors stay referenced by the list until the launch is enqueued."""
     active = False
     pending = []
-    WIDE_ROWS = int(os.environ.get("ST_WIDE_ROWS", "2048"))   # token counts from here up take st_wgrad_wide (8192 until round 5; a 4-utterance shard's
-                                                              # 3,120 rows: step 1.675 -> 1.639 ms with the wide kernel; the variable: development)
+    WIDE_ROWS = 2048          # token counts from here up take st_wgrad_wide (8192 until round 5; a 4-utterance shard's
+                              # 3,120 rows: step 1.675 -> 1.639 ms with the wide kernel)
     ROWS_PER_SPLIT = 3072     # ~48 k-steps per workgroup; measured on config 2 (24060 rows): 8 splits beat 4, 12 and 16
 
     @staticmethod

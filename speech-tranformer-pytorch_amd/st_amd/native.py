@@ -708,29 +708,23 @@ def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None):
     nb, dP, G, xa, ra, ga, drop, dsa, dga, dba, dbia = head if head else (0,) + z[:10]
     d_ff, bits, msc, dH, xb, rb, gb, dsb, dgb, dbb, dbib = ffn if ffn else (0, None, 1.0) + z[:8]
     O, Ores, dctx, delta = tail if tail else z[:4]
-    wide = next((t for t in (G, xa, xb, O) if t is not None), None)     # whichever d_model-wide operand the call has
-    d = 512 if (wide is not None and wide.shape[1] == 512) else 256     # (d_model 512: csrc/st_rowchain_pipe512_bwd.cuh - HEAD + FFN + TAIL)
-    if d == 512:
-        if not (head and ffn and tail) or nb not in (0, 6) or ds_in is not None:
-            raise ValueError("row_chain_bwd (d_model 512): HEAD, FFN and TAIL are required, head blocks 0 or 6, and no ds_in "
-                             "(the chain starts from its HEAD)")
-        n_blocks = 2 * nb + 4 * (d_ff // 256) + 4
-    else:
-        n_blocks = nb + (2 * (d_ff // 256) if ffn else 0) + (1 if tail else 0)
+    if any(t is not None and t.dim() == 2 and t.shape[1] == 512 for t in (G, xa, ds_in, xb, O)):
+        raise ValueError("row_chain_bwd: the backward chain exists at width 256 only (d_model 512 takes the per-GEMM kernels)")
+    n_blocks = nb + (2 * (d_ff // 256) if ffn else 0) + (1 if tail else 0)
     if n_blocks != chain.n_blocks or chain.stream.numel() != 8 * (n_blocks * 16 + wfrag_depth()) * 512:
         raise ValueError("row_chain_bwd: the fragment stream does not match the chain")
-    for t, cols, ld, name in ((dP, 256 * nb, None, "dP"), (G, d, None, "G"), (xa, d, d, "xhat_a"), (dsa, d, d, "ds_a"),
-                              (ds_in, d, d, "ds_in"), (dH, d_ff, d_ff, "dH"), (xb, d, d, "xhat_b"), (dsb, d, d, "ds_b"),
-                              (O, d, None, "O"), (Ores, d, None if O is None else O.stride(0), "Ores"), (dctx, d, None, "dctx")):
+    for t, cols, ld, name in ((dP, 256 * nb, None, "dP"), (G, 256, None, "G"), (xa, 256, 256, "xhat_a"), (dsa, 256, 256, "ds_a"),
+                              (ds_in, 256, 256, "ds_in"), (dH, d_ff, d_ff, "dH"), (xb, 256, 256, "xhat_b"), (dsb, 256, 256, "ds_b"),
+                              (O, 256, None, "O"), (Ores, 256, None if O is None else O.stride(0), "Ores"), (dctx, 256, None, "dctx")):
         if t is not None:
             _mat(t, BF16, name, min_rows=M, cols=cols, ld=ld)
     if ffn:
         if bits is None:
             raise ValueError("row_chain_bwd: relu_bits must be the int64 buffer the forward chain wrote (chain_mask_words(M, d_ff) words)")
-        _vec(bits, I64, chain_mask_words(M, d_ff, d), "relu_bits")
-    for v, n, name in ((ra, M, "rstd_a"), (ga, d, "gamma_a"), (dga, d, "dgamma_a"), (dba, d, "dbeta_a"), (dbia, d, "dbias_a"),
-                       (rb, M, "rstd_b"), (gb, d, "gamma_b"), (dgb, d, "dgamma_b"), (dbb, d, "dbeta_b"), (dbib, d, "dbias_b"),
-                       (delta, (d // 64) * M, "delta")):
+        _vec(bits, I64, chain_mask_words(M, d_ff), "relu_bits")
+    for v, n, name in ((ra, M, "rstd_a"), (ga, 256, "gamma_a"), (dga, 256, "dgamma_a"), (dba, 256, "dbeta_a"), (dbia, 256, "dbias_a"),
+                       (rb, M, "rstd_b"), (gb, 256, "gamma_b"), (dgb, 256, "dgamma_b"), (dbb, 256, "dbeta_b"), (dbib, 256, "dbias_b"),
+                       (delta, 4 * M, "delta")):
         _vec(v, F32, n, name)
     if head is None and ds_in is None:
         raise ValueError("row_chain_bwd: without head the chain needs ds_in")
@@ -742,16 +736,8 @@ def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None):
     # encoder-sized HEAD + FFN + TAIL launches leave their LayerNorm column sums in a per-workgroup workspace (no atomics: 251 workgroups
     # adding to the same 768 floats queue for ~8 us per launch); st_colsum_fold adds it to the gradients - at once, or with the deferred
     # weight gradients (flush_colsum_folds)
-    ws_rows = 0 if d == 512 else load()._cdll.st_row_chain_bwd_colsum_rows(int(M), int(head is not None), int(d_ff), int(tail is not None))
-    cws = torch.empty(ws_rows * 1536, dtype=F32, device=wide.device) if ws_rows > 0 else None
-    if d == 512:
-        rc = load().st_row_chain512_bwd(
-            _stream(), M, chain.stream.data_ptr(), n_blocks, int(chain.next_blocks), int(nb), _p(dP), 0 if dP is None else dP.stride(0),
-            _p(G), 0 if G is None else G.stride(0), _p(xa), _p(ra), _p(ga), sd[0], sd[1], sd[2], sd[3], _p(dsa), _p(dga), _p(dba),
-            _p(dbia), int(d_ff), _p(bits), float(msc), _p(dH), _p(xb), _p(rb), _p(gb), _p(dsb), _p(dgb), _p(dbb), _p(dbib),
-            _p(O), _p(Ores), O.stride(0), _p(dctx), dctx.stride(0), _p(delta))
-        _check(rc, "st_row_chain512_bwd")
-        return
+    ws_rows = load()._cdll.st_row_chain_bwd_colsum_rows(int(M), int(head is not None), int(d_ff), int(tail is not None))
+    cws = torch.empty(ws_rows * 1536, dtype=F32, device=chain.stream.device) if ws_rows > 0 else None
     rc = load().st_row_chain_bwd(
         _stream(), M, chain.stream.data_ptr(), n_blocks, int(chain.next_blocks), int(nb), _p(dP), 0 if dP is None else dP.stride(0),
         _p(G), 0 if G is None else G.stride(0), _p(xa), _p(ra), _p(ga), sd[0], sd[1], sd[2], sd[3], _p(dsa), _p(dga), _p(dba),

@@ -715,9 +715,10 @@ def drain_collective_watchdog(limit_s: float = 5.0) -> str:
     synchronisation.  Now: the process group's flight recorder says for every collective whether the watchdog thread
     has RETIRED it (the ``retired`` flag of ``_dump_nccl_trace`` entries is set by that thread, when it drops the work from its
     list - unlike ``onlyActive`` and the ``state`` strings, which the dump call fills in itself by querying the events) - poll until
-    every recorded collective is retired.  The recorder must be on (``TORCH_NCCL_TRACE_BUFFER_SIZE`` > 0 before the process group is
-    created: ``enable_collective_recorder()``, called by bench.py and dp.GradReducer's callers); where it is off or absent the fixed
-    wait remains as the fallback (``ST_DP_DRAIN_MS``, default 300).  -> which of the two happened ("recorder" / "sleep")."""
+    every recorded collective is retired.  The recorder must be on: whoever creates the process group sets the environment variable
+    ``TORCH_NCCL_TRACE_BUFFER_SIZE`` (the ring's size in collectives; 512 everywhere here) before ``init_process_group`` -
+    ``dp.init_from_env`` does, and so do bench.py ``--force-dp`` and the tests that make a one-rank group themselves; where it is
+    off or absent the fixed wait remains as the fallback (``ST_DP_DRAIN_MS``, default 300).  -> which of the two happened ("recorder" / "sleep")."""
     torch.cuda.synchronize()
     fallback_s = float(os.environ.get("ST_DP_DRAIN_MS", "300")) / 1e3
     dump = getattr(torch._C._distributed_c10d, "_dump_nccl_trace", None) if torch.distributed.is_available() else None
@@ -736,13 +737,6 @@ def drain_collective_watchdog(limit_s: float = 5.0) -> str:
             pass
     time.sleep(fallback_s)
     return "sleep"
-
-
-def enable_collective_recorder(entries: int = 512) -> None:
-    """Call BEFORE torch.distributed.init_process_group: turns ProcessGroupNCCL's flight recorder on (a ring of the last `entries`
-    collectives; off by default in this build), which is what lets drain_collective_watchdog() wait for the watchdog instead of
-    sleeping."""
-    os.environ.setdefault("TORCH_NCCL_TRACE_BUFFER_SIZE", str(entries))
 
 
 class _Captured:

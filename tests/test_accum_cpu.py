@@ -165,6 +165,9 @@ def test_wrappers_check_their_arguments_before_any_launch():
         nv.adam_clip_win(f, f, f, f, f[0], f[0], None, 1.0, 0.9, 0.98, 1e-9, None)
     with pytest.raises(ValueError, match="required"):
         nv.grad_norm_win(f, f, f[0], None, None, w)
+    # the backward row chain exists at width 256 only: a 512-wide operand is refused by name, before the chain is looked at
+    with pytest.raises(ValueError, match="width 256 only"):
+        nv.row_chain_bwd(None, 8, head=(0, None, torch.zeros(8, 512, dtype=torch.bfloat16)) + (None,) * 8)
 
 
 # ---- 2. a window against the fp64 full-batch truth --------------------------------------------------------------------------

@@ -59,12 +59,20 @@ def test_plans_decline_what_the_kernels_do_not_serve():
         m.decoder.use_row_chains = False
         assert m.decoder.row_chains(a) is None
         m8 = model(256, 8, 512)                 # d_k 32: forward chains yes, backward chains no (the delta epilogue's heads are 64 wide)
-        assert m8.encoder.row_chains(arena_of(m8)).use_bwd is False
+        a8 = arena_of(m8)
+        e8 = m8.encoder.row_chains(a8)
+        assert e8.use_bwd is False and e8.bwd is None and [c.n_blocks for c in e8.e] == [1 + 4]
+        assert chains.ChainHub.of(a8).sets == [e8.set]          # no backward set is built, none is refreshed after an optimizer step
+        d8 = m8.decoder.row_chains(a8)
+        assert d8.use_bwd is False and d8.bwd1 is None and d8.bwd2 is None
+        assert [c.n_blocks for c in d8.f1] == [2, 2] and [c.n_blocks for c in d8.f2] == [1 + 4 + 3, 1 + 4]
+        assert chains.ChainHub.of(a8).sets == [e8.set, d8.set]
         for bad in (model(128, 4, 256), model(256, 4, 384)):
             ab = arena_of(bad)
             assert bad.encoder.row_chains(ab) is None and bad.decoder.row_chains(ab) is None
-        m5 = model(512, 8, 1024)                # config 3's width: forward and backward chains for the encoder (st_row_chain512[_bwd])
+        m5 = model(512, 8, 1024)                # config 3's width: forward chains for the encoder (st_row_chain512), no backward chains
         a5 = arena_of(m5)
         e5 = m5.encoder.row_chains(a5)
-        assert e5 is not None and not e5.use_bwd and [c.n_blocks for c in e5.e] == [4 + 16] and [c.n_blocks for c in e5.bwd] == [16 + 4]
+        assert e5 is not None and e5.use_bwd is False and e5.bwd is None and [c.n_blocks for c in e5.e] == [4 + 16]
         assert m5.decoder.row_chains(a5) is None
+        assert chains.ChainHub.of(a5).sets == [e5.set]

@@ -145,10 +145,10 @@ def test_infeasible_utterances_agree_with_the_plan():
 def test_new_exports_in_header_binding_and_library():
     names = ["st_ctc_loss_ws_kib", "st_ctc_loss_fwd", "st_ctc_loss_grad"]
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "st_hip.h")).read(), flags=re.S)
-    assert native.ABI_VERSION == 6 and re.search(r"#define\s+ST_ABI_VERSION\s+6\b", text)
+    assert native.ABI_VERSION == 7 and re.search(r"#define\s+ST_ABI_VERSION\s+7\b", text)
     decl = dict(re.findall(r"\bint\s+(st_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", text, flags=re.S))
     lib = native.load()
-    assert lib.st_version() == 6
+    assert lib.st_version() == 7
     syms = subprocess.run(["nm", "-D", "--defined-only", native.lib_path()], check=True, capture_output=True, text=True).stdout
     exported = set(re.findall(r"\bT\s+(st_[a-z0-9_]+)", syms))
     for n in names:

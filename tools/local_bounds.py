@@ -122,31 +122,6 @@ def chain_bwd():
             note("row_chain_bwd", nm, res[F32][nm], res[F64][nm])
 
 
-def chain512_bwd():
-    d, dff, nb = 512, 1024, 6
-    wp, w1, w2, wo = g(3 * d, d, seed=1, scale=d ** -0.5), g(dff, d, seed=2, scale=d ** -0.5), g(d, dff, seed=3, scale=dff ** -0.5), g(d, d, seed=4, scale=d ** -0.5)
-    blocks = chains.encoder512_blocks_bwd(wo, w1, w2, wp)
-    for M in (5, 1000, 24060):
-        dP, G = g(M, 3 * d, seed=5, scale=0.3), g(M, d, seed=6, scale=0.3)
-        xa, xb = g(M, d, seed=8), g(M, d, seed=9)
-        ra, rb = g(M, seed=10, dtype=F32).abs() + 0.5, g(M, seed=11, dtype=F32).abs() + 0.5
-        ga, gb = g(d, seed=12, dtype=F32) * 0.2 + 1, g(d, seed=13, dtype=F32) * 0.2 + 1
-        H = torch.relu(g(M, dff, seed=14))
-        O, Ores = g(M, d, seed=15), g(M, d, seed=16, scale=2.0 ** -9)
-        res = {}
-        for dt in (F32, F64):
-            Z = lambda *s, dt_=BF16: torch.zeros(*s, dtype=dt_)
-            o = dict(ds_a=Z(M, d), dga=Z(d, dt_=F32) + 1, dba=Z(d, dt_=F32) + 2, dbia=Z(d, dt_=F32) + 3, dH=Z(M, dff), ds_b=Z(M, d),
-                     dgb=Z(d, dt_=F32) - 1, dbb=Z(d, dt_=F32) - 2, dbib=Z(d, dt_=F32) - 3, dctx=Z(M, d), delta=Z(8 * M, dt_=F32))
-            em.row_chain_bwd(chains.Chain(None, len(blocks), blocks), M,
-                             head=(nb, dP, G, xa, ra, ga, None, o["ds_a"], o["dga"], o["dba"], o["dbia"]),
-                             ffn=(dff, em.relu_bits_from(H, d), 1.0, o["dH"], xb, rb, gb, o["ds_b"], o["dgb"], o["dbb"], o["dbib"]),
-                             tail=(O, Ores, o["dctx"], o["delta"]), dtype=dt, dbias_rounded=True)
-            res[dt] = o
-        for nm in res[F32]:
-            note("row_chain512_bwd", nm, res[F32][nm], res[F64][nm])
-
-
 def probs_and_ctc():
     """st_attn_probs' fp32 maps (the emulation's softmax in fp32 against fp64) and st_ctc_dlogits' bf16 gradient."""
     for case in tk.PRESCALED_CASES:
@@ -280,7 +255,6 @@ if __name__ == "__main__":
               drop=em.Drop(torch.tensor([1234567], dtype=I32), 3, 0.2))
     ln_family()
     chain_bwd()
-    chain512_bwd()
     probs_and_ctc()
     dense()
     probs()
