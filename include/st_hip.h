@@ -620,8 +620,11 @@ int stx_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, i
  * number are spelled out by the tests that came with it).  This section - prefix `st2_`, version ST2_VERSION returned by
  * st2_version() - is checked DIFFERENTLY: its test derives the expected set from this header and compares it with the binding
  * (native.EXT2_SIGNATURES, parsed by the same native.parse_extension with prefix "st2"), with the library's exported
- * symbols and with the extern "C" definitions under csrc/.  So the NEXT entry point is declared here and ST2_VERSION is
- * bumped; no further prefix is needed.  Conventions, library and return codes are those of the two sections above.
+ * symbols and with the extern "C" definitions under csrc/.  That was meant to let the next entry point join this section
+ * with a bump of ST2_VERSION - but the tests that came with gradient accumulation spell out ST2_VERSION == 3, so this
+ * section is frozen like the two before it.  The rule that holds: a NEW SECTION (next prefix, own version macro, parsed by
+ * native.parse_extension(text, prefix)) is needed whenever the previous section's version number is pinned from outside this
+ * header; see the third section at the end.  Conventions, library and return codes are those of the two sections above.
  *
  * SpecAugment (Park et al. 2019: time and frequency masks; the time warp is not built) inside the training step.  Masks are
  * drawn per utterance from the dropout seed in device memory (drop_seed above), so a captured graph draws new masks on every
@@ -709,6 +712,36 @@ int st2_adam_clip_win(st_stream_t stream, long long n, float* p, float* g, float
 /* The window's results, then a fresh window (one thread; after the update in stream order): out f32 [4] = {win[1] / win[0],
  * win[2] / win[0], win[0], win[3]} = {loss, plain NLL, denominator, micro-batches}; win = 0. */
 int st2_window_close(st_stream_t stream, float* win, float* out);
+
+/* ---- Third extension section ---------------------------------------------------------------------------------------------
+ * Prefix `st3_`, version ST3_VERSION returned by st3_version(); bound as native.EXT3_SIGNATURES / native.EXT3_VERSION and
+ * checked at load like the other two.  It exists because ST2_VERSION is asserted by value outside this header (see above); its
+ * own test derives the expected set from this header, so an entry point may join it with a bump of ST3_VERSION until
+ * somebody pins that number too.
+ *
+ * Forward-only validation (csrc/st_eval.hip; st_amd/evaluate.py:EvalStep): teacher-forced loss, NLL and token accuracy of a
+ * dev set without a host read per batch.  Neither kernel traps, allocates or reads host memory: both can be captured.
+ *
+ * st3_ce_eval_fwd: logits f32 [R, ldl], the first V columns are vocabulary (columns >= V - the -1e30 padding of the vocabulary
+ * projection - are never read); target / target_index / ignore_index address the ground truth as in st_ce_fwd; (confidence,
+ * smooth, zero_col) is the smoothed target of stx_ce_smooth_fwd, (1, 0, -1) the plain loss.  One workgroup per row, one pass.
+ * rows f32 [R, 4] (16-byte aligned), row r = {row_loss, row_nll, row_hit, state}:
+ *   state 1 (a counted token): row_loss = stx_ce_smooth_fwd's row_loss (the criterion's numerator), row_nll = lse - x[t],
+ *           row_hit = 1 if argmax_{v < V} x[v] == t else 0 - among equal maxima the LOWEST column is the arg-max;
+ *   state 0 (t == ignore_index): 0, 0, 0;
+ *   state 2 (t outside [0, V) and not ignore_index - a stray label): 0, 0, 0.  The row is counted, never dereferenced. */
+#define ST3_VERSION 1
+int st3_version(void);
+int st3_ce_eval_fwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                    const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col, float* rows);
+/* One workgroup sums the R rows of st3_ce_eval_fwd in a fixed order, in fp64 (no atomics; the result depends on the rows
+ * alone), and ADDS into the epoch accumulator acc, fp64 [8] on the device:
+ *   [0] loss numerator   [1] loss denominator: the batch's counted tokens, or *denom (device f32 scalar) when denom is given
+ *   [2] NLL sum          [3] counted tokens     [4] hits     [5] batches noted     [6] stray labels (state 2)     [7] spare
+ * fp64 because an epoch adds 10^6 - 10^7 token losses: an fp32 running sum loses the digits checkpoints are compared by.
+ * last f32 [4] (16-byte aligned) is overwritten with this batch's {loss = numerator / denominator, nll, accuracy, tokens};
+ * a batch without a counted token leaves nan means (0 / 0), as nn.CrossEntropyLoss does.  R may be 0. */
+int st3_eval_note(st_stream_t stream, const float* rows, int R, const float* denom, double* acc, float* last);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@
 ``arena``       flat parameter / gradient / bf16-shadow storage
 ``dp``          RCCL data-parallel gradient all-reduce (the Horovod role)
 ``trainer``     the train.py step sequence
+``evaluate``    forward-only validation: dev-set loss, NLL and token accuracy on the device
 
 The drop-in nn.Modules live in the sibling package ``transformer`` (same import
 paths as the reference).  There is no CPU fallback: without the HIP library and

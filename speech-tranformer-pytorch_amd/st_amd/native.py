@@ -82,6 +82,8 @@ SIGNATURES, ABI_VERSION, _EPI = parse_header(_read_header())
 EXT_SIGNATURES, EXT_VERSION = parse_extension(_read_header())
 # ... and its second extension section (st2_*: SpecAugment, the optimizer's options, gradient accumulation)
 EXT2_SIGNATURES, EXT2_VERSION = parse_extension(_read_header(), "st2")
+# ... and its third (st3_*: forward-only validation)
+EXT3_SIGNATURES, EXT3_VERSION = parse_extension(_read_header(), "st3")
 (EPI_BF16, EPI_BF16_RELU, EPI_F32, EPI_BF16_MASK, EPI_BF16_ADD, EPI_F32_ATOMIC, EPI_F32_ATOMIC_T, EPI_BF16_DELTA) = (
     _EPI["ST_" + k] for k in ("EPI_BF16", "EPI_BF16_RELU", "EPI_F32", "EPI_BF16_MASK", "EPI_BF16_ADD", "EPI_F32_ATOMIC",
                               "EPI_F32_ATOMIC_T", "EPI_BF16_DELTA"))
@@ -184,7 +186,8 @@ def load(build_if_missing: bool = True):
     if ver != ABI_VERSION:
         raise RuntimeError("libst_hip.so at %s has ABI version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
                            % (path, ver, ABI_VERSION))
-    for entry, want, what in (("stx_version", EXT_VERSION, "extension"), ("st2_version", EXT2_VERSION, "second extension")):
+    for entry, want, what in (("stx_version", EXT_VERSION, "extension"), ("st2_version", EXT2_VERSION, "second extension"),
+                              ("st3_version", EXT3_VERSION, "third extension")):
         try:
             getattr(cdll, entry).restype = _c_int
             xver = int(getattr(cdll, entry)())
@@ -193,7 +196,8 @@ def load(build_if_missing: bool = True):
         if xver != want:
             raise RuntimeError("libst_hip.so at %s has %s version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
                                % (path, what, xver, want))
-    bound = list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT2_SIGNATURES.items())
+    bound = (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT2_SIGNATURES.items())
+             + list(EXT3_SIGNATURES.items()))
     missing = [name for name, _ in bound if not hasattr(cdll, name)]
     if missing:
         raise RuntimeError("libst_hip.so at %s lacks %s: rebuild it (python __graft_entry__.py)" % (path, ", ".join(missing)))
@@ -1767,6 +1771,71 @@ def adam_clip_win(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, win,
                                     step.data_ptr(), _p(gnorm), float(max_norm), float(beta1), float(beta2), float(eps),
                                     float(grad_scale), _p(found_inf), _p(avg), float(decay), int(bool(decay_warmup)),
                                     win.data_ptr()), "st2_adam_clip_win")
+
+
+# ---- forward-only validation: per-row loss / NLL / arg-max hit and the epoch accumulator (st3_, version 1) -------------------
+F64 = torch.float64
+
+
+def _eval_arg(who, t, dtype, shape, name, optional=False):
+    """The FORM of an argument: a contiguous tensor of ``dtype`` and exactly ``shape`` (an extent of None: any), or None for an
+    optional one - ValueError naming the argument, whatever device it lives on (the device comes after every form: _eval_gpu)."""
+    if t is None:
+        if optional:
+            return
+        raise ValueError("%s: %s is required" % (who, name))
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.dim() != len(shape)
+            or any(w is not None and w != n for w, n in zip(shape, t.shape))):
+        raise ValueError("%s: %s must be a contiguous %s tensor of shape %s (None = any extent), got %s" % (
+            who, name, dtype, list(shape), (t.dtype, tuple(t.shape), t.stride()) if isinstance(t, torch.Tensor) else type(t).__name__))
+
+
+def _eval_gpu(who, **tensors):
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(_NO_GPU % ("%s: %s" % (who, name)))
+
+
+def ce_eval_fwd(logits, target, ignore_index, confidence, smooth, zero_col, rows, V=None, index=None):
+    """rows (f32 [R, 4]) = per logits row {criterion numerator, plain NLL, 1 if the arg-max over the first V columns is the
+    target, state} - see st3_ce_eval_fwd.  logits f32 [R, ldl] with ldl >= V (unit column stride); V: the TRUE vocabulary
+    (None: every column); index: row r's target is target.view(-1)[index[r]].  (confidence, smooth, zero_col) as
+    ce_smooth_fwd; (1, 0, -1) is the plain loss.  A target outside [0, V) that is not ignore_index is counted, never followed."""
+    who = "ce_eval_fwd"
+    if not isinstance(logits, torch.Tensor) or logits.dtype != F32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("%s: logits must be an f32 row matrix with unit column stride" % who)
+    R, ldl = logits.shape[0], logits.stride(0)
+    V = logits.shape[1] if V is None else int(V)
+    if not 0 < V <= logits.shape[1] or (R > 1 and ldl < V):
+        raise ValueError("%s: V = %d must lie in [1, %d]: ldl >= V (logits has %d columns, leading dimension %d)"
+                         % (who, V, logits.shape[1], logits.shape[1], ldl))
+    if int(zero_col) >= V:
+        raise ValueError("%s: zero_col = %d must be below V = %d (negative: none)" % (who, int(zero_col), V))
+    if not isinstance(target, torch.Tensor) or target.dtype != I64 or not target.is_contiguous() or (index is None and target.numel() < R):
+        raise ValueError("%s: target must be a contiguous int64 tensor%s" % (who, "" if index is not None else " of at least R = %d elements" % R))
+    _eval_arg(who, rows, F32, (R, 4), "rows")
+    _eval_arg(who, index, I64, (R,), "index", optional=True)
+    _eval_gpu(who, logits=logits, target=target, rows=rows, index=index)
+    _tag("ce_eval_fwd", R, V, 0, io=(4.0 * R * V, 24.0 * R))
+    _check(load().st3_ce_eval_fwd(_stream(), logits.data_ptr(), ldl, R, V, target.data_ptr(), _p(index), int(ignore_index),
+                                  float(confidence), float(smooth), int(zero_col), rows.data_ptr()), "st3_ce_eval_fwd")
+    return rows
+
+
+def eval_note(rows, acc, last, denom=None):
+    """One batch joins the epoch (st3_eval_note): the rows of ce_eval_fwd are summed in a fixed order in fp64 and ADDED into
+    acc (f64 [8]: loss numerator, loss denominator, NLL sum, tokens, hits, batches, stray labels, spare); last (f32 [4]) = this
+    batch's (loss, nll, accuracy, tokens).  denom (1-element f32 device tensor or None): the batch's loss denominator instead
+    of its token count."""
+    who = "eval_note"
+    _eval_arg(who, rows, F32, (None, 4), "rows")
+    _eval_arg(who, acc, F64, (8,), "acc")
+    _eval_arg(who, last, F32, (4,), "last")
+    _eval_arg(who, denom, F32, (1,), "denom", optional=True)
+    _eval_gpu(who, rows=rows, acc=acc, last=last, denom=denom)
+    _tag("eval_note", rows.shape[0], io=(16.0 * rows.shape[0],))
+    _check(load().st3_eval_note(_stream(), rows.data_ptr(), rows.shape[0], _p(denom), acc.data_ptr(), last.data_ptr()), "st3_eval_note")
+    return last
 
 
 def probe_tr16(inp, out):

@@ -476,55 +476,8 @@ class TrainStep:
 
     def _bucket_call(self, inputs, input_lengths, targets, target_lengths, ground_truth):
         """Bucket mode: stage the batch into the bucket's static buffers, refresh the device-resident lengths, replay."""
-        T_cap, L_cap = self.bucket
-        B, T, Fd = inputs.shape
-        L = targets.shape[1]
-        if T > T_cap or L > L_cap or ground_truth.shape[1] > L_cap:
-            raise ValueError("TrainStep(bucket=%r): batch of %d frames / %d tokens does not fit" % (self.bucket, T, L))
-        caps = None                   # the first packed capacity the batch fits (None: the padded bucket)
-        if self.bucket_rows is not None:
-            n_in, n_tgt = int(input_lengths.sum()), int(target_lengths.sum())
-            caps = next((c for c in self.bucket_rows if n_in <= c[0] and n_tgt <= c[1]), None)
-        packed = caps is not None
-        key = (B, Fd, inputs.dtype, str(inputs.device), caps)
-        st = self._buckets.get(key)
-        if st is None:
-            from .functional import Rows
-            dev = inputs.device
-            st = _Bucket()
-            st.x = torch.zeros(B, T_cap, Fd, dtype=inputs.dtype, device=dev)
-            st.tok = torch.zeros(B, L_cap, dtype=targets.dtype, device=dev)
-            # (one spare element behind the padded ground truth: the target of the rows a packed bucket leaves unassigned;
-            # it stays 0 = ignore_index)
-            st.gt_flat = torch.zeros(B * L_cap + 1, dtype=ground_truth.dtype, device=dev)
-            st.gt = st.gt_flat[:B * L_cap].view(B, L_cap)
-            in_cap, tgt_cap = caps if packed else (None, None)
-            st.layouts = (Rows.bucket(B, T_cap, dev, rows=in_cap), Rows.bucket(B, L_cap, dev, rows=tgt_cap))
-            if hasattr(self.model, "prepare_layouts"):          # chain plans, work lists: before any capture
-                from .functional import attn_work
-                self.model.prepare_layouts(torch.full((B,), T_cap), torch.full((B,), L_cap), L_cap, dev)
-                ir, tr = st.layouts
-                dk, nh = getattr(self.model, "_d_k", 64), getattr(self.model, "_n_head", 0)
-                attn_work(ir, ir, False, dk, nh), attn_work(tr, tr, True, dk, nh), attn_work(tr, ir, False, dk, nh)
-                tr.scatter_index(L_cap)
-            self._buckets[key] = st
-        st.x[:, :T].copy_(inputs, non_blocking=True)
-        if T < T_cap:
-            st.x[:, T:].zero_()                                  # no frame of an earlier batch survives behind a length
-        st.tok.zero_()
-        st.tok[:, :L].copy_(targets, non_blocking=True)
-        st.gt.zero_()                                            # padding positions: ground truth 0 = ignore_index
-        st.gt[:, :ground_truth.shape[1]].copy_(ground_truth, non_blocking=True)
-        st.layouts[0].set_lengths(input_lengths)
-        st.layouts[1].set_lengths(target_lengths)
-        if hasattr(self.model, "prepare_layouts"):
-            # the encoder self-attention's work lists follow the batch (longest utterance first); the decoder's attentions
-            # are a handful of short workgroups either way
-            from .functional import refresh_attn_work
-            ir = st.layouts[0]
-            refresh_attn_work(ir, ir, False, getattr(self.model, "_d_k", 64), getattr(self.model, "_n_head", 0),
-                              input_lengths.tolist(), input_lengths.tolist())
-        batch = (st.x, input_lengths, st.tok, target_lengths, st.gt_flat if packed else st.gt)
+        st, batch, packed = stage_bucket("TrainStep", self.model, self._buckets, self.bucket, self.bucket_rows, inputs,
+                                         input_lengths, targets, target_lengths, ground_truth)
         if not self.use_graph:
             return self._eager(batch, layouts=st.layouts)
         if st.cap is None:
@@ -703,6 +656,64 @@ class _Bucket:
     def __init__(self):
         self.x = self.tok = self.gt = self.gt_flat = self.layouts = self.cap = self.tails = None
         self.seen = 0
+
+
+def stage_bucket(who, model, buckets, bucket, bucket_rows, inputs, input_lengths, targets, target_lengths, ground_truth):
+    """The staging of one batch into a bucket, shared by the step drivers (TrainStep, evaluate.EvalStep): the batch is copied
+    into the bucket's static padded buffers, the lengths (packed capacities: the offsets too) are refreshed on the device, the
+    encoder's work lists follow the batch.  ``buckets``: the driver's dict of _Bucket by (B, feature, dtype, device,
+    capacity); a missing one is created here - buffers, Rows.bucket layouts, chain plans and work lists, all before any capture.
+    -> (the _Bucket, the batch to run: static tensors + this batch's lengths, whether the layouts are packed)."""
+    T_cap, L_cap = bucket
+    B, T, Fd = inputs.shape
+    L = targets.shape[1]
+    if T > T_cap or L > L_cap or ground_truth.shape[1] > L_cap:
+        raise ValueError("%s(bucket=%r): batch of %d frames / %d tokens does not fit" % (who, bucket, T, L))
+    caps = None                   # the first packed capacity the batch fits (None: the padded bucket)
+    if bucket_rows is not None:
+        n_in, n_tgt = int(input_lengths.sum()), int(target_lengths.sum())
+        caps = next((c for c in bucket_rows if n_in <= c[0] and n_tgt <= c[1]), None)
+    packed = caps is not None
+    key = (B, Fd, inputs.dtype, str(inputs.device), caps)
+    st = buckets.get(key)
+    if st is None:
+        from .functional import Rows
+        dev = inputs.device
+        st = _Bucket()
+        st.x = torch.zeros(B, T_cap, Fd, dtype=inputs.dtype, device=dev)
+        st.tok = torch.zeros(B, L_cap, dtype=targets.dtype, device=dev)
+        # (one spare element behind the padded ground truth: the target of the rows a packed bucket leaves unassigned;
+        # it stays 0 = ignore_index)
+        st.gt_flat = torch.zeros(B * L_cap + 1, dtype=ground_truth.dtype, device=dev)
+        st.gt = st.gt_flat[:B * L_cap].view(B, L_cap)
+        in_cap, tgt_cap = caps if packed else (None, None)
+        st.layouts = (Rows.bucket(B, T_cap, dev, rows=in_cap), Rows.bucket(B, L_cap, dev, rows=tgt_cap))
+        if hasattr(model, "prepare_layouts"):          # chain plans, work lists: before any capture
+            from .functional import attn_work
+            model.prepare_layouts(torch.full((B,), T_cap), torch.full((B,), L_cap), L_cap, dev)
+            ir, tr = st.layouts
+            dk, nh = getattr(model, "_d_k", 64), getattr(model, "_n_head", 0)
+            attn_work(ir, ir, False, dk, nh), attn_work(tr, tr, True, dk, nh), attn_work(tr, ir, False, dk, nh)
+            tr.scatter_index(L_cap)
+        buckets[key] = st
+    st.x[:, :T].copy_(inputs, non_blocking=True)
+    if T < T_cap:
+        st.x[:, T:].zero_()                                  # no frame of an earlier batch survives behind a length
+    st.tok.zero_()
+    st.tok[:, :L].copy_(targets, non_blocking=True)
+    st.gt.zero_()                                            # padding positions: ground truth 0 = ignore_index
+    st.gt[:, :ground_truth.shape[1]].copy_(ground_truth, non_blocking=True)
+    st.layouts[0].set_lengths(input_lengths)
+    st.layouts[1].set_lengths(target_lengths)
+    if hasattr(model, "prepare_layouts"):
+        # the encoder self-attention's work lists follow the batch (longest utterance first); the decoder's attentions
+        # are a handful of short workgroups either way
+        from .functional import refresh_attn_work
+        ir = st.layouts[0]
+        refresh_attn_work(ir, ir, False, getattr(model, "_d_k", 64), getattr(model, "_n_head", 0),
+                          input_lengths.tolist(), input_lengths.tolist())
+    batch = (st.x, input_lengths, st.tok, target_lengths, st.gt_flat if packed else st.gt)
+    return st, batch, packed
 
 
 def drain_collective_watchdog(limit_s: float = 5.0) -> str:
