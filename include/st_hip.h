@@ -30,16 +30,18 @@ extern "C" {
 
 typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C: no HIP header needed */
 
-/* Library ABI version, bumped on any signature change (2: round 5's k_prescaled / dense attention / grad_scale arguments;
- * 3, 4: round 6 - 4 added the column-sum workspace of st_row_chain_bwd; 5: the joint CTC / attention beam search; 6: st_ctc_loss_*; 7: st_row_chain512_bwd removed).  A host binding must refuse a library whose st_version() differs from the header it was written against:
+/* Library ABI version.  A host binding must refuse a library whose st_version() differs from the header it was written against:
  * through ctypes / dlsym a stale libst_hip.so would be called with shifted arguments.
  * This header is the ONLY copy of the ABI: every source under csrc/ is compiled against it (csrc/st_common.cuh includes it, so a
  * definition that disagrees with its declaration stops the build), st_version() returns this macro, and st_amd/native.py
  * parses this file at import for its argument types, ABI_VERSION and the EPI_* constants.  To add an entry point: declare
  * it here (parameter types: pointers, st_stream_t, int, unsigned, float, long, long long - the binding refuses anything
- * else), define it in csrc/, write its wrapper in st_amd/native.py - and bump the number if an existing signature moved.
- * (Entry points added since version 6 go into the extension section at the end of this file, which says why.) */
-#define ST_ABI_VERSION 7
+ * else), define it in csrc/, write its wrapper in st_amd/native.py.
+ * The number is not a counter.  It is a FINGERPRINT of the declarations below (their names, order and parameter types, and the
+ * ST_EPI_* values; comments, whitespace, parameter names and `const` do not count), computed by native.abi_fingerprint():
+ *   change a declaration - importing st_amd.native fails - paste the number its message prints.
+ * So it cannot be forgotten, and there is nothing in it to assert by value: no test may spell it out. */
+#define ST_ABI_VERSION 1713104753
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -471,10 +473,23 @@ int st_cast_bf16(st_stream_t stream, const float* src, void* dst, long long n);
  * scalars.  n: elements, a multiple of 4; p, g, m (exp_avg), v (exp_avg_sq): fp32 [n].
  * grad_scale: the buffer holds gradient / grad_scale - 1 / world behind a SUMMING all-reduce (train_multi.py:161-163:
  * Horovod averages), 1 otherwise; the factor is applied together with the clip coefficient (g is left holding the
- * clipped, averaged gradient), *gnorm must be the norm of the scaled gradient (st_grad_norm with the same grad_scale). */
+ * clipped, averaged gradient), *gnorm must be the norm of the scaled gradient (st_grad_norm with the same grad_scale).
+ * Three optional pointers add behaviour, one kernel body (csrc/st_optim.cuh); each may be NULL independently, and with all
+ * three NULL this is the plain update above.
+ * found_inf (device f32, or NULL): when *found_inf != 0 the launch writes nothing - p, g, m, v and avg keep their bits (g is
+ * NOT clipped or scaled either).  Pass guard of st_grad_norm.  With found_inf NULL and avg NULL the results are bit-identical
+ * to the plain update.
+ * avg (fp32 [n], or NULL): the exponential moving average of the parameters, updated after the parameter update in the same
+ * pass: avg += w * (p_new - avg), w = 1.0f - d in fp32, d = decay, or with decay_warmup != 0 d = min(decay, (1 + t) / (10 + t))
+ * with t = *step (the count of APPLIED updates, already incremented).  decay in [0, 1]; w == 0 leaves avg untouched.
+ * win (device f32 [4], or NULL): the update over a gradient-accumulation window (st_accum_note below).  The coefficient every
+ * gradient element is multiplied by is min(1, max_norm / (*gnorm + 1e-6)) * grad_scale / win[0], one fp32 scalar formed before
+ * the loop; *gnorm is st_grad_norm's with the same win.  g is left holding ZEROS, not the clipped gradient: the update is the
+ * next window's zero_grad.  Under *found_inf != 0 the zeros are the only thing written - p, m, v and avg keep their bits.  With
+ * win[0] == 1 and found_inf clear p, m, v and avg equal those of the form with win NULL bit for bit. */
 int st_adam_clip(st_stream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
                  const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
-                 float grad_scale);
+                 float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup, const float* win);
 
 /* Zero the unassigned tail rows of a list of row matrices in one launch (packed bucket layouts: the rows behind the
  * batch's last utterance belong to nobody; the kernels never write them, so they must read as zeros).  table (device,
@@ -487,10 +502,20 @@ int st_zero(st_stream_t stream, void* ptr, long long bytes);
 /* total_norm of clip_grad_norm_ (train.py:45) over the flat fp32 gradient buffer g [n] (n % 4 == 0) as one launch:
  * *gnorm = grad_scale * ||g||_2 (partials added in a fixed order, fp64), and - when step is not NULL - *step += 1, the optimiser's
  * step count st_adam_clip then reads.  scratch: st_grad_norm_blocks() + 1 floats owned by the caller, the last one
- * zero before the first call (the kernel leaves it zero). */
+ * zero before the first call (the kernel leaves it zero).  Two optional pointers add behaviour, one kernel body
+ * (csrc/st_optim.cuh); with either of them step is required.
+ * guard (device f32 [2], or NULL): a verdict.  Same grid, same partial sums, same fixed-order fp64 merge: for finite input *gnorm
+ * equals the value of the form without a guard bit for bit.  The workgroup that finishes the reduction is the single writer of
+ * the verdict: a finite norm -> *step += 1, guard[0] = 0; otherwise step is left alone, guard[0] = 1 and guard[1] += 1 (a running
+ * count of skipped steps).  *gnorm is written in both cases.  Non-finite: any NaN or +-inf element, and ALSO finite elements
+ * whose sum of squares overflows fp32 within one workgroup's partial sum (the partials are fp32; the norm is then inf).
+ * win (device f32 [4], or NULL): the norm over a gradient-accumulation window (st_accum_note below), *gnorm = grad_scale * ||g||
+ * / win[0].  Without a guard there is no verdict (*step += 1 always); with a guard the verdict is ALSO bad when win[0] <= 0 (a
+ * window without a single token: nothing to divide by).  Partial sums and the fixed-order fp64 merge are unchanged: with
+ * win[0] == 1 and finite input *gnorm equals that of the form with win NULL bit for bit (a division by 1.0f is exact). */
 int st_grad_norm_blocks(void);
 int st_grad_norm(st_stream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
-                 float grad_scale);
+                 float grad_scale, float* guard, const float* win);
 
 /* Cross-entropy over ragged logits rows (train.py:40,120: nn.CrossEntropyLoss(ignore_index = 0), mean over the
  * non-ignored tokens).  logits f32 [R, ldl] (V valid columns; padding columns holding -1e30 may be counted as valid),
@@ -583,19 +608,6 @@ int st_probe_mfma(st_stream_t stream, const void* A, const void* Bt, float* D);
  * (s_memrealtime, 100 MHz)} of wave 0 in out[2 wg], out[2 wg + 1]: MHz = 100 ticks / wall.  ~2 ms at iters = 30000. */
 int st_clock_probe(st_stream_t stream, long long* out, int n_wg, int iters);
 
-/* ---- Extension section -------------------------------------------------------------------------------------------------
- * Entry points added after the base ABI above was frozen.  The base section is pinned from outside this header: the
- * project's tests count its `int st_*` declarations, compare them with the definitions in csrc/ and with the binding's
- * table, and assert the value of the base version macro - so a new entry point can neither join that list nor bump that
- * number without rewriting those checks.  New entry points are therefore declared HERE, in the same header (it stays the one
- * copy of the ABI: compiled into every source, parsed by st_amd/native.py), under the prefix `stx_` and with a version of
- * their own: STX_VERSION, returned by stx_version(), bumped whenever an stx_* signature changes or one is added.  The
- * binding parses this section by the same parameter rules into native.EXT_SIGNATURES / native.EXT_VERSION and refuses a
- * library whose stx_version() differs, exactly as it does for st_version().  Nothing else distinguishes the two sections:
- * same conventions, same library, same return codes. */
-#define STX_VERSION 1
-int stx_version(void);
-
 /* Cross-entropy against a smoothed target over ragged logits rows (transformer/Loss.py:LabelSmoothingLoss;
    nn.CrossEntropyLoss(label_smoothing = e)).  Row r with target t != ignore_index has the target
    distribution q[v] = confidence (v == t), 0 (v == zero_col, v != t; zero_col < 0: none), smooth (every other v < V);
@@ -606,27 +618,16 @@ int stx_version(void);
    any sum.  target / target_index / ignore_index / lse / row_loss as st_ce_fwd.  zero_col >= V: refused.
    At (confidence 1, smooth 0, zero_col -1, denom NULL) both calls compute st_ce_fwd / st_ce_bwd bit for bit: the kernels
    are one body (csrc/st_ce.cuh). */
-int stx_ce_smooth_fwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
-                      const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
-                      const float* denom, float* lse, float* row_loss, float* sums);
+int st_ce_smooth_fwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                     const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
+                     const float* denom, float* lse, float* row_loss, float* sums);
 /* dlogits bf16 [R, ldd] = (Q exp(logits - lse) - q) * *grad_out / D on the non-ignored rows, 0 on ignored rows and in
    columns >= V. */
-int stx_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
-                      const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
-                      const float* denom, const float* lse, const float* sums, const float* grad_out, void* dlogits, int ldd);
+int st_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                     const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
+                     const float* denom, const float* lse, const float* sums, const float* grad_out, void* dlogits, int ldd);
 
-/* ---- Second extension section ------------------------------------------------------------------------------------------
- * The stx_ section above is pinned from outside this header in the same way as the base section (its names and its version
- * number are spelled out by the tests that came with it).  This section - prefix `st2_`, version ST2_VERSION returned by
- * st2_version() - is checked DIFFERENTLY: its test derives the expected set from this header and compares it with the binding
- * (native.EXT2_SIGNATURES, parsed by the same native.parse_extension with prefix "st2"), with the library's exported
- * symbols and with the extern "C" definitions under csrc/.  That was meant to let the next entry point join this section
- * with a bump of ST2_VERSION - but the tests that came with gradient accumulation spell out ST2_VERSION == 3, so this
- * section is frozen like the two before it.  The rule that holds: a NEW SECTION (next prefix, own version macro, parsed by
- * native.parse_extension(text, prefix)) is needed whenever the previous section's version number is pinned from outside this
- * header; see the third section at the end.  Conventions, library and return codes are those of the two sections above.
- *
- * SpecAugment (Park et al. 2019: time and frequency masks; the time warp is not built) inside the training step.  Masks are
+/* SpecAugment (Park et al. 2019: time and frequency masks; the time warp is not built) inside the training step.  Masks are
  * drawn per utterance from the dropout seed in device memory (drop_seed above), so a captured graph draws new masks on every
  * replay; they are applied by the kernel that converts the features to bf16 rows anyway, so no extra byte moves.
  *
@@ -639,109 +640,68 @@ int stx_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, i
  * Width 0 = no mask; masked elements become 0.0 (the mean after CMVN).  Masks live in RAW coordinates: frames of the
  * unstacked utterance, bins of one raw frame.
  *
- * st2_specaug_plan: table int32 [B, n_time + n_freq, 2] = (start, width) of every mask of every utterance, one small launch.
+ * st_specaug_plan: table int32 [B, n_time + n_freq, 2] = (start, width) of every mask of every utterance, one small launch.
  * T_raw = (len[b] - 1) * interval + 1 + right (0 when len[b] < 1) with len on the DEVICE: pass (interval 1, right 0) with raw
  * lengths, or the stacking geometry with the lengths of already stacked / subsampled rows - then T_raw is the last raw frame
  * that can appear in a row, plus one.  n_time + n_freq <= 64. */
-#define ST2_VERSION 3
-int st2_version(void);
-int st2_specaug_plan(st_stream_t stream, const unsigned* seed, unsigned salt, const int* len, int B, int interval, int right,
-                     int n_time, int time_width, int time_ratio_permille, int n_freq, int freq_width, int mel_bins, int* table);
+int st_specaug_plan(st_stream_t stream, const unsigned* seed, unsigned salt, const int* len, int B, int interval, int right,
+                    int n_time, int time_width, int time_ratio_permille, int n_freq, int freq_width, int mel_bins, int* table);
 /* st_pack_rows with the masks of `table` applied: x fp32 [B, T, F], F = mel_bins * (1 + left + right), rows ALREADY stacked /
  * subsampled as st_feat_stack would (left = right = 0, interval = 1: plain frames).  Column c = context slot k = c / mel_bins,
  * bin f = c % mel_bins; row r, slot k hold raw frame src(k, r * interval) by st_feat_stack's rule (csrc/st_augment.cuh) with
- * the utterance's T_raw (as st2_specaug_plan computes it) for the raw length - the true raw length is not known here, so a
+ * the utterance's T_raw (as st_specaug_plan computes it) for the raw length - the true raw length is not known here, so a
  * right-context slot that the reference's right-width indexing lays over another slot counts as the right context.  An
  * element is zeroed iff its source frame lies in a time mask or its bin in a frequency mask.  mel_bins % 4 == 0. */
-int st2_pack_rows_aug(st_stream_t stream, const float* x, int B, int T, int F, const int* off, const int* len, void* out,
-                      const int* table, int n_time, int n_freq, int mel_bins, int left, int right, int interval);
+int st_pack_rows_aug(st_stream_t stream, const float* x, int B, int T, int F, const int* off, const int* len, void* out,
+                     const int* table, int n_time, int n_freq, int mel_bins, int left, int right, int interval);
 /* st_feat_stack with the masks of `table` (planned with the raw lengths in_len, interval 1, right 0; mel_bins = F) applied
  * after CMVN and before stacking. */
-int st2_feat_stack_aug(st_stream_t stream, const float* x, int B, int T, int F, const int* in_len, const float* stats, int left,
-                       int right, int interval, const int* out_off, const int* out_len, int max_out_len, void* out, int ld,
-                       const int* table, int n_time, int n_freq);
+int st_feat_stack_aug(st_stream_t stream, const float* x, int B, int T, int F, const int* in_len, const float* stats, int left,
+                      int right, int interval, const int* out_off, const int* out_len, int max_out_len, void* out, int ld,
+                      const int* table, int n_time, int n_freq);
 
-/* ---- st2_, version 2: the optimizer update skips non-finite gradients and keeps averaged weights ---------------------------
- * st_grad_norm with a verdict.  Same grid, same partial sums, same fixed-order fp64 merge: for finite input *gnorm equals
- * st_grad_norm's value bit for bit.  The workgroup that finishes the reduction is the single writer of the verdict in guard
- * (device f32 [2]): a finite norm -> *step += 1, guard[0] = 0; otherwise step is left alone, guard[0] = 1 and guard[1] += 1 (a
- * running count of skipped steps).  *gnorm is written in both cases.  Non-finite: any NaN or +-inf element, and ALSO finite
- * elements whose sum of squares overflows fp32 within one workgroup's partial sum (the partials are fp32; the norm is then
- * inf).  step and guard are required; scratch as st_grad_norm (the two may share one). */
-int st2_grad_norm_guard(st_stream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
-                        float grad_scale, float* guard);
-/* st_adam_clip plus two optional behaviours, one kernel body with it (csrc/st_optim.cuh); with found_inf NULL and avg NULL the
- * results are bit-identical to st_adam_clip.
- * found_inf (device f32, or NULL): when *found_inf != 0 the launch writes nothing - p, g, m, v and avg keep their bits (g is
- * NOT clipped or scaled either).  Pass guard of st2_grad_norm_guard.
- * avg (fp32 [n], or NULL): the exponential moving average of the parameters, updated after the parameter update in the same
- * pass: avg += w * (p_new - avg), w = 1.0f - d in fp32, d = decay, or with decay_warmup != 0 d = min(decay, (1 + t) / (10 + t))
- * with t = *step (the count of APPLIED updates, already incremented).  decay in [0, 1]; w == 0 leaves avg untouched. */
-int st2_adam_clip_avg(st_stream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
-                      const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
-                      float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup);
-/* Exchange two fp32 buffers in place (n % 4 == 0, both 16-byte aligned, not overlapping): the averaged weights go under the
- * model and back.  A pointer swap is not possible - parameter views and captured graphs hold addresses into the arena. */
-int st2_swap_f32(st_stream_t stream, float* a, float* b, long long n);
+/* Exchange two fp32 buffers in place (n % 4 == 0, both 16-byte aligned, not overlapping): the averaged weights (st_adam_clip's
+ * avg) go under the model and back.  A pointer swap is not possible - parameter views and captured graphs hold addresses into
+ * the arena. */
+int st_swap_f32(st_stream_t stream, float* a, float* b, long long n);
 
-/* ---- st2_, version 3: gradient accumulation over micro-batches with an on-device denominator --------------------------------
+/* Gradient accumulation over micro-batches with an on-device denominator.
  * A WINDOW of micro-batches adds the gradients of their SUM losses into the flat gradient buffer; what the window divides by
  * (its token count, say) is known only after the last one, and never on the host.  win (device f32 [4]) is the window's state:
  * [0] the denominator, [1] the sum of row losses, [2] the sum of plain NLL, [3] micro-batches noted.  Counts stay exact in
  * fp32 up to 2^24.
  *
- * st2_accum_note: one micro-batch joins the window, after its loss forward (one thread).  sums: the f32 [4] that
- * stx_ce_smooth_fwd left (run with a denominator of 1.0).  win[1] += sums[0]; win[2] += sums[3] * sums[1] (nothing when
+ * st_accum_note: one micro-batch joins the window, after its loss forward (one thread).  sums: the f32 [4] that
+ * st_ce_smooth_fwd left (run with a denominator of 1.0).  win[1] += sums[0]; win[2] += sums[3] * sums[1] (nothing when
  * sums[1] == 0: the NLL mean of no token is 0 / 0, their sum is 0); win[3] += 1; win[0] += *d - or, d NULL, win[0] = 1 (a SUM
  * criterion: no division).  out[0] = the micro-batch's own loss, sums[0] / *d (d NULL: sums[0]).  d may point into sums. */
-int st2_accum_note(st_stream_t stream, const float* sums, const float* d, float* win, float* out);
-/* st2_grad_norm_guard over a window: *gnorm = grad_scale * ||g|| / win[0].  guard may be NULL (no verdict: *step += 1 always);
- * with a guard the verdict is ALSO bad when win[0] <= 0 (a window without a single token: nothing to divide by).  Partial sums
- * and the fixed-order fp64 merge are unchanged: with win[0] == 1 and finite input *gnorm equals st2_grad_norm_guard's bit for
- * bit (a division by 1.0f is exact). */
-int st2_grad_norm_win(st_stream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
-                      float grad_scale, float* guard, const float* win);
-/* st2_adam_clip_avg over a window.  The coefficient every gradient element is multiplied by is
- * min(1, max_norm / (*gnorm + 1e-6)) * grad_scale / win[0], one fp32 scalar formed before the loop; *gnorm is
- * st2_grad_norm_win's.  g is left holding ZEROS, not the clipped gradient: the update is the next window's zero_grad.  Under
- * *found_inf != 0 the zeros are the only thing written - p, m, v and avg keep their bits.  With win[0] == 1 and found_inf clear
- * p, m, v and avg equal st2_adam_clip_avg's bit for bit. */
-int st2_adam_clip_win(st_stream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
-                      const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
-                      float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup, const float* win);
-/* The window's results, then a fresh window (one thread; after the update in stream order): out f32 [4] = {win[1] / win[0],
+int st_accum_note(st_stream_t stream, const float* sums, const float* d, float* win, float* out);
+/* (The window's norm and update: st_grad_norm and st_adam_clip with their win pointer.)
+ * The window's results, then a fresh window (one thread; after the update in stream order): out f32 [4] = {win[1] / win[0],
  * win[2] / win[0], win[0], win[3]} = {loss, plain NLL, denominator, micro-batches}; win = 0. */
-int st2_window_close(st_stream_t stream, float* win, float* out);
+int st_window_close(st_stream_t stream, float* win, float* out);
 
-/* ---- Third extension section ---------------------------------------------------------------------------------------------
- * Prefix `st3_`, version ST3_VERSION returned by st3_version(); bound as native.EXT3_SIGNATURES / native.EXT3_VERSION and
- * checked at load like the other two.  It exists because ST2_VERSION is asserted by value outside this header (see above); its
- * own test derives the expected set from this header, so an entry point may join it with a bump of ST3_VERSION until
- * somebody pins that number too.
- *
- * Forward-only validation (csrc/st_eval.hip; st_amd/evaluate.py:EvalStep): teacher-forced loss, NLL and token accuracy of a
+/* Forward-only validation (csrc/st_eval.hip; st_amd/evaluate.py:EvalStep): teacher-forced loss, NLL and token accuracy of a
  * dev set without a host read per batch.  Neither kernel traps, allocates or reads host memory: both can be captured.
  *
- * st3_ce_eval_fwd: logits f32 [R, ldl], the first V columns are vocabulary (columns >= V - the -1e30 padding of the vocabulary
+ * st_ce_eval_fwd: logits f32 [R, ldl], the first V columns are vocabulary (columns >= V - the -1e30 padding of the vocabulary
  * projection - are never read); target / target_index / ignore_index address the ground truth as in st_ce_fwd; (confidence,
- * smooth, zero_col) is the smoothed target of stx_ce_smooth_fwd, (1, 0, -1) the plain loss.  One workgroup per row, one pass.
+ * smooth, zero_col) is the smoothed target of st_ce_smooth_fwd, (1, 0, -1) the plain loss.  One workgroup per row, one pass.
  * rows f32 [R, 4] (16-byte aligned), row r = {row_loss, row_nll, row_hit, state}:
- *   state 1 (a counted token): row_loss = stx_ce_smooth_fwd's row_loss (the criterion's numerator), row_nll = lse - x[t],
+ *   state 1 (a counted token): row_loss = st_ce_smooth_fwd's row_loss (the criterion's numerator), row_nll = lse - x[t],
  *           row_hit = 1 if argmax_{v < V} x[v] == t else 0 - among equal maxima the LOWEST column is the arg-max;
  *   state 0 (t == ignore_index): 0, 0, 0;
  *   state 2 (t outside [0, V) and not ignore_index - a stray label): 0, 0, 0.  The row is counted, never dereferenced. */
-#define ST3_VERSION 1
-int st3_version(void);
-int st3_ce_eval_fwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
-                    const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col, float* rows);
-/* One workgroup sums the R rows of st3_ce_eval_fwd in a fixed order, in fp64 (no atomics; the result depends on the rows
+int st_ce_eval_fwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                   const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col, float* rows);
+/* One workgroup sums the R rows of st_ce_eval_fwd in a fixed order, in fp64 (no atomics; the result depends on the rows
  * alone), and ADDS into the epoch accumulator acc, fp64 [8] on the device:
  *   [0] loss numerator   [1] loss denominator: the batch's counted tokens, or *denom (device f32 scalar) when denom is given
  *   [2] NLL sum          [3] counted tokens     [4] hits     [5] batches noted     [6] stray labels (state 2)     [7] spare
  * fp64 because an epoch adds 10^6 - 10^7 token losses: an fp32 running sum loses the digits checkpoints are compared by.
  * last f32 [4] (16-byte aligned) is overwritten with this batch's {loss = numerator / denominator, nll, accuracy, tokens};
  * a batch without a counted token leaves nan means (0 / 0), as nn.CrossEntropyLoss does.  R may be 0. */
-int st3_eval_note(st_stream_t stream, const float* rows, int R, const float* denom, double* acc, float* last);
+int st_eval_note(st_stream_t stream, const float* rows, int R, const float* denom, double* acc, float* last);
 
 #ifdef __cplusplus
 }

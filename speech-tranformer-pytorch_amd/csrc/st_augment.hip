@@ -1,7 +1,7 @@
 // SpecAugment inside the training step (gfx950): the per-utterance mask plan drawn from the dropout seed in device memory, and
 // the two feature kernels of st_misc.hip - the ragged pack and the feature front-end - with the masks applied on the way to
 // bf16 rows.  HBM- and launch-bound like their neighbours: same grids, same access widths, the utterance's mask table (at most
-// 64 pairs) in LDS.  The draw is spelled out in include/st_hip.h (st2_ section).
+// 64 pairs) in LDS.  The draw is spelled out in include/st_hip.h (st_specaug_plan).
 #include "st_augment.cuh"
 
 namespace {
@@ -102,11 +102,9 @@ bool bad_masks(int n_time, int n_freq) { return n_time < 0 || n_freq < 0 || n_ti
 
 }  // namespace
 
-extern "C" int st2_version(void) { return ST2_VERSION; }
-
-extern "C" int st2_specaug_plan(hipStream_t stream, const unsigned* seed, unsigned salt, const int* len, int B, int interval,
-                                int right, int n_time, int time_width, int time_ratio_permille, int n_freq, int freq_width,
-                                int mel_bins, int* table) {
+extern "C" int st_specaug_plan(hipStream_t stream, const unsigned* seed, unsigned salt, const int* len, int B, int interval,
+                               int right, int n_time, int time_width, int time_ratio_permille, int n_freq, int freq_width,
+                               int mel_bins, int* table) {
   if (bad_masks(n_time, n_freq) || interval < 1 || right < 0 || time_width < 0 || freq_width < 0 || mel_bins < 1 ||
       time_ratio_permille < 0 || time_ratio_permille > 1000 || !seed)
     return -1;
@@ -119,9 +117,9 @@ extern "C" int st2_specaug_plan(hipStream_t stream, const unsigned* seed, unsign
   return 0;
 }
 
-extern "C" int st2_pack_rows_aug(hipStream_t stream, const float* x, int B, int T, int F, const int* off, const int* len,
-                                 void* out, const int* table, int n_time, int n_freq, int mel_bins, int left, int right,
-                                 int interval) {
+extern "C" int st_pack_rows_aug(hipStream_t stream, const float* x, int B, int T, int F, const int* off, const int* len,
+                                void* out, const int* table, int n_time, int n_freq, int mel_bins, int left, int right,
+                                int interval) {
   if (bad_masks(n_time, n_freq) || left < 0 || right < 0 || right > left || interval < 1 || mel_bins < 4 || (mel_bins & 3) ||
       (long long)mel_bins * (1 + left + right) != F)
     return -1;
@@ -133,10 +131,10 @@ extern "C" int st2_pack_rows_aug(hipStream_t stream, const float* x, int B, int 
   return 0;
 }
 
-extern "C" int st2_feat_stack_aug(hipStream_t stream, const float* x, int B, int T, int F, const int* in_len,
-                                  const float* stats, int left, int right, int interval, const int* out_off,
-                                  const int* out_len, int max_out_len, void* out, int ld, const int* table, int n_time,
-                                  int n_freq) {
+extern "C" int st_feat_stack_aug(hipStream_t stream, const float* x, int B, int T, int F, const int* in_len,
+                                 const float* stats, int left, int right, int interval, const int* out_off,
+                                 const int* out_len, int max_out_len, void* out, int ld, const int* table, int n_time,
+                                 int n_freq) {
   if (bad_masks(n_time, n_freq) || left < 0 || right < 0 || right > left || interval < 1 || F < 1 ||
       ld < (long long)F * (1 + left + right))
     return -1;

@@ -1,6 +1,6 @@
 // Cross-entropy over ragged logits rows: ONE kernel body for the plain loss (st_ce_fwd / st_ce_bwd in st_misc.hip,
-// train.py:40,120: nn.CrossEntropyLoss(ignore_index = 0)) and for the loss against a smoothed target (stx_ce_smooth_fwd /
-// stx_ce_smooth_bwd in st_loss.hip: transformer/Loss.py:LabelSmoothingLoss, nn.CrossEntropyLoss(label_smoothing = e)),
+// train.py:40,120: nn.CrossEntropyLoss(ignore_index = 0)) and for the loss against a smoothed target (st_ce_smooth_fwd /
+// st_ce_smooth_bwd in st_loss.hip: transformer/Loss.py:LabelSmoothingLoss, nn.CrossEntropyLoss(label_smoothing = e)),
 // templated on `bool Smooth`.  Every smoothing term sits behind `if constexpr (Smooth)`: the <false> instantiation is the
 // kernel the plain loss always ran - same loads, same reduction order - and <true> at (confidence 1, smooth 0, no zero
 // column, no denominator) computes the same bits, because its extra factors are then exactly 1 and 0.

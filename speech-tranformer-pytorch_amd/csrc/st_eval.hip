@@ -1,6 +1,6 @@
-// Forward-only validation over ragged logits rows (gfx950): the st3_* extension section of include/st_hip.h.
-// st3_ce_eval_fwd: per row, in ONE pass over the logits, the criterion's numerator (the formula of ce_fwd_kernel<true> in
-// st_ce.cuh), the plain NLL and whether the arg-max over the vocabulary is the target.  st3_eval_note: the fixed-order fp64
+// Forward-only validation over ragged logits rows (gfx950): st_ce_eval_fwd / st_eval_note of include/st_hip.h.
+// st_ce_eval_fwd: per row, in ONE pass over the logits, the criterion's numerator (the formula of ce_fwd_kernel<true> in
+// st_ce.cuh), the plain NLL and whether the arg-max over the vocabulary is the target.  st_eval_note: the fixed-order fp64
 // sum of those rows, ADDED into an epoch accumulator in device memory - no host read between the first batch of a validation
 // pass and its last.  The training loss kernels (st_ce.cuh) are shared with the training step and stay as they are: this is a
 // body of its own in a translation unit of its own.  Unlike them it never traps: a target outside [0, V) that is not the
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void ce_eval_fwd_kernel(const float* __restric
     f32x4 out = {0.f, 0.f, 0.f, 0.f};      // {row_loss, row_nll, row_hit, state}; ignored rows: all zero
     if (t != ignore) {
       if (t < 0 || t >= V) {
-        out[3] = 2.f;                      // a stray label: counted by st3_eval_note, contributes nothing else
+        out[3] = 2.f;                      // a stray label: counted by st_eval_note, contributes nothing else
       } else {
         const float l = gm + __logf(red_s[0] + red_s[1] + red_s[2] + red_s[3]);
         const float xt = row[t];
@@ -132,11 +132,9 @@ __global__ __launch_bounds__(256) void eval_note_kernel(const float* __restrict_
 
 }  // namespace
 
-extern "C" int st3_version(void) { return ST3_VERSION; }
-
-extern "C" int st3_ce_eval_fwd(hipStream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
-                               const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
-                               float* rows) {
+extern "C" int st_ce_eval_fwd(hipStream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                              const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
+                              float* rows) {
   if (R <= 0) return 0;
   if (!logits || !target || !rows || V <= 0 || ldl < V || zero_col >= V || ((size_t)rows & 15)) return -1;
   hipLaunchKernelGGL(ce_eval_fwd_kernel, dim3(R), dim3(256), 0, stream, logits, ldl, V, target, target_index, ignore_index,
@@ -145,7 +143,7 @@ extern "C" int st3_ce_eval_fwd(hipStream_t stream, const float* logits, int ldl,
   return 0;
 }
 
-extern "C" int st3_eval_note(hipStream_t stream, const float* rows, int R, const float* denom, double* acc, float* last) {
+extern "C" int st_eval_note(hipStream_t stream, const float* rows, int R, const float* denom, double* acc, float* last) {
   if (R < 0 || (R > 0 && !rows) || !acc || !last || ((size_t)rows & 15) || ((size_t)last & 15) || ((size_t)acc & 7)) return -1;
   hipLaunchKernelGGL(eval_note_kernel, dim3(1), dim3(256), 0, stream, rows, R, denom, acc, last);
   ST_CHECK_LAUNCH();

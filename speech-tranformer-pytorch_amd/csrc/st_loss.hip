@@ -1,4 +1,4 @@
-// Label-smoothed cross-entropy over ragged logits rows (gfx950): the stx_* extension section of include/st_hip.h.
+// Label-smoothed cross-entropy over ragged logits rows (gfx950): st_ce_smooth_fwd / st_ce_smooth_bwd of include/st_hip.h.
 // transformer/Loss.py:LabelSmoothingLoss (the recipe's label smoothing 0.1, with the reference's PAD-column quirk and its
 // division by all rows) and nn.CrossEntropyLoss(label_smoothing = e) as the SAME two-launch forward / one-launch backward
 // the plain loss runs (st_ce_fwd / st_ce_bwd, st_misc.hip): these entry points launch the <true> instantiation of the
@@ -7,11 +7,9 @@
 #include "st_hip.h"
 #include "st_ce.cuh"
 
-extern "C" int stx_version(void) { return STX_VERSION; }
-
-extern "C" int stx_ce_smooth_fwd(hipStream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
-                                 const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
-                                 const float* denom, float* lse, float* row_loss, float* sums) {
+extern "C" int st_ce_smooth_fwd(hipStream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                                const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
+                                const float* denom, float* lse, float* row_loss, float* sums) {
   if (R <= 0) return 0;
   if (!logits || !target || !lse || !row_loss || !sums || V <= 0 || ldl < V || zero_col >= V) return -1;
   const CeSmooth sp{confidence, smooth, zero_col < 0 ? -1 : zero_col, denom};
@@ -23,10 +21,10 @@ extern "C" int stx_ce_smooth_fwd(hipStream_t stream, const float* logits, int ld
   return 0;
 }
 
-extern "C" int stx_ce_smooth_bwd(hipStream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
-                                 const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
-                                 const float* denom, const float* lse, const float* sums, const float* grad_out, void* dlogits,
-                                 int ldd) {
+extern "C" int st_ce_smooth_bwd(hipStream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
+                                const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
+                                const float* denom, const float* lse, const float* sums, const float* grad_out, void* dlogits,
+                                int ldd) {
   if (R <= 0) return 0;
   if (!logits || !target || !lse || !sums || !grad_out || !dlogits || V <= 0 || ldl < V || ldd < V || (ldd & 7) || zero_col >= V)
     return -1;

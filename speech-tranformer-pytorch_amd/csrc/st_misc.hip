@@ -4,7 +4,10 @@
 // feature axis (coalesced 256-512 B per wave per row).
 #include "st_common.cuh"
 #include "st_ce.cuh"
-#include "st_optim.cuh"
+
+#ifndef ST_ADAM_SC1
+#define ST_ADAM_SC1 0      // development: st_zero's stores write-through (store16_wt), as the optimizer kernels' switch of st_optim.cuh
+#endif
 
 namespace {
 
@@ -243,8 +246,6 @@ __global__ void cast_bf16_kernel(const float* __restrict__ src, bf16* __restrict
     *reinterpret_cast<bf16x8*>(dst + i * 8) = o;
   }
 }
-
-// (the optimizer update's two kernels - adam_clip_kernel, grad_norm_kernel - live in st_optim.cuh, shared with st_optim.hip)
 
 // Zero the rows [*valid, cap) of a list of row matrices - the rows a packed bucket layout (st_amd.functional.Rows.bucket
 // with a capacity) leaves to no utterance - in ONE launch per step instead of a whole-matrix memset per buffer (72 of
@@ -1104,37 +1105,6 @@ extern "C" int st_zero(hipStream_t stream, void* ptr, long long bytes) {
   int blocks = (int)((n16 + 1023) / 1024);
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(zero_kernel, dim3(blocks), dim3(256), 0, stream, (f32x4*)ptr, n16);
-  ST_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int st_grad_norm_blocks(void) { return 1024; }
-
-extern "C" int st_grad_norm(hipStream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
-                            float grad_scale) {
-  // scratch: st_grad_norm_blocks() + 1 floats, the last one (the ticket) zero before the first call
-  if (n <= 0 || (n & 3) || !g || !scratch || !gnorm) return -1;
-  const size_t n4 = (size_t)n / 4;
-  // one workgroup per CU: the tickets are same-address atomics, which serialise (~15 ns each: 1024 workgroups spent 15 us on
-  // them, ce_fwd's 1,200 once 43 us)
-  int blocks = (int)((n4 + 1023) / 1024);
-  if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(grad_norm_kernel<false>, dim3(blocks), dim3(1024), 0, stream, g, n4, scratch, reinterpret_cast<unsigned*>(scratch + 1024),
-                     gnorm, step, grad_scale, (float*)nullptr, (const float*)nullptr);
-  ST_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int st_adam_clip(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
-                            const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
-                            float grad_scale) {
-  if (n <= 0) return 0;
-  if ((n & 3) || !p || !g || !m || !v || !lr || !step) return -1;
-  const size_t n4 = (size_t)n / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL((adam_clip_kernel<false, false>), dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, lr, step, gnorm, max_norm, beta1,
-                     beta2, eps, grad_scale, (const float*)nullptr, (float*)nullptr, 0.0f, 0, (const float*)nullptr);
   ST_CHECK_LAUNCH();
   return 0;
 }

@@ -1,8 +1,8 @@
-// The two kernels of the optimizer update over the flat parameter arena, each ONE body for two entry points (as st_ce.cuh
-// serves both cross-entropy kernels): st_misc.hip instantiates the plain forms (st_grad_norm, st_adam_clip), st_optim.hip the
-// forms with a non-finite verdict and an averaged copy of the weights (st2_grad_norm_guard, st2_adam_clip_avg).  The template
+// The two kernels of the optimizer update over the flat parameter arena, each ONE body for every form of its entry point
+// (st_grad_norm, st_adam_clip in st_optim.hip, which instantiates them all): the plain forms, and the forms with a non-finite
+// verdict (GUARD) and an averaged copy of the weights (AVG), chosen by which optional pointers the caller gives.  The template
 // switches only ADD statements: with both off the arithmetic, its order and the stores are those of the plain kernels.
-// A third switch, WIN, serves gradient accumulation over micro-batches (st2_grad_norm_win, st2_adam_clip_win): the gradient
+// A third switch, WIN, serves gradient accumulation over micro-batches (the win pointer of both entry points): the gradient
 // buffer holds a SUM whose denominator win[0] is a device scalar known only after the last micro-batch; dividing by 1.0f is
 // exact, so at win[0] == 1 the WIN forms compute what the forms without it compute, bit for bit.
 #pragma once
@@ -19,10 +19,10 @@ namespace {
 // (bias corrections from the step count, denom = sqrt(v) / sqrt(bc2) + eps, p -= lr / bc1 * m / denom); the clipped
 // gradient is written back, as clip_grad_norm_ leaves it.  lr / step / gnorm are device scalars, so a captured graph
 // replays with the current learning rate.
-// st2_adam_clip_avg: GUARD - a non-zero *found_inf makes the whole launch a no-op, nothing is written; AVG - the exponential
+// found_inf / avg: GUARD - a non-zero *found_inf makes the whole launch a no-op, nothing is written; AVG - the exponential
 // moving average of the parameters, avg += w * (p_new - avg) in the same pass, w = 1 - d, d = decay or (decay_warmup)
 // min(decay, (1 + step) / (10 + step)).  Two switches, so that the guard alone streams exactly what the plain kernel streams.
-// st2_adam_clip_win: WIN - the coefficient is also divided by win[0] (still ONE scalar, formed before the loop), and ZEROS are
+// win: WIN - the coefficient is also divided by win[0] (still ONE scalar, formed before the loop), and ZEROS are
 // stored to g where the clipped gradient would go: the update is the next window's zero_grad at no extra traffic.  Under WIN a
 // non-zero *found_inf still clears g (the skipped window's sum must not leak into the next one) and writes nothing else.
 template <bool GUARD, bool AVG, bool WIN = false>
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, f
   // grad_scale: what the buffer still has to be multiplied by to be THE gradient (1 / world behind a summing all-reduce:
   // the rank average costs no pass of its own); *gnorm_p is the norm of the scaled gradient (st_grad_norm's grad_scale)
   float coef = (gnorm_p ? fminf(max_norm / (*gnorm_p + 1e-6f), 1.0f) : 1.0f) * grad_scale;
-  if (WIN) coef = coef / *win;      // the window's denominator; *gnorm_p is the norm of the DIVIDED gradient (st2_grad_norm_win)
+  if (WIN) coef = coef / *win;      // the window's denominator; *gnorm_p is the norm of the DIVIDED gradient (st_grad_norm with win)
   const float bc1 = 1.0f - powf(beta1, step), bc2 = 1.0f - powf(beta2, step);
   const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2);
   float w = 0.0f;
@@ -83,9 +83,9 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, f
 // index order: the result does not depend on the arrival order), writes *gnorm, advances the optimiser's step counter
 // (*step += 1, optional) and resets the ticket for the next launch.  Replaces torch.linalg.vector_norm (52 MB at 2.6 TB/s
 // plus a memset) and the separate step increment: three graph nodes -> one.
-// GUARD (st2_grad_norm_guard): the same single writer also leaves the verdict - a non-finite norm does not advance the step,
+// GUARD (guard given): the same single writer also leaves the verdict - a non-finite norm does not advance the step,
 // sets guard[0] and counts up guard[1]; a finite one clears guard[0].
-// WIN (st2_grad_norm_win): the norm is divided by the window's denominator win[0], and a denominator <= 0 is a bad verdict too.
+// WIN (win given): the norm is divided by the window's denominator win[0], and a denominator <= 0 is a bad verdict too.
 template <bool GUARD, bool WIN = false>
 __global__ __launch_bounds__(1024) void grad_norm_kernel(const float* __restrict__ g, size_t n4, float* partial, unsigned* ticket,
                                                         float* __restrict__ gnorm, float* step, float grad_scale, float* guard,

@@ -1,8 +1,9 @@
-// The optimizer update with a guard against non-finite gradients and an averaged copy of the weights (gfx950): the forms of
-// st_grad_norm / st_adam_clip that st_optim.cuh builds from the same bodies, and the in-place exchange of two flat buffers that
-// puts the averaged weights under the model.  HBM streams like their neighbours in st_misc.hip: same grids, 16-byte accesses.
-// Gradient accumulation over micro-batches adds the WIN forms of the two kernels and the two one-thread launches that keep the
-// window's state (denominator, loss sums, count) in device memory: st2_accum_note, st2_window_close.
+// The optimizer update (gfx950): st_grad_norm and st_adam_clip - every instantiation of the two bodies of st_optim.cuh, chosen by
+// which optional pointers are given (a guard against non-finite gradients, an averaged copy of the weights, a gradient-
+// accumulation window) - and the in-place exchange of two flat buffers that puts the averaged weights under the model.  HBM
+// streams like their neighbours in st_misc.hip: 16-byte accesses.  Gradient accumulation over micro-batches adds the two
+// one-thread launches that keep the window's state (denominator, loss sums, count) in device memory: st_accum_note,
+// st_window_close.
 #include "st_optim.cuh"
 
 namespace {
@@ -17,7 +18,7 @@ __global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float*
   }
 }
 
-// One micro-batch noted in the window (see st2_accum_note in include/st_hip.h); one thread, plain stores.
+// One micro-batch noted in the window (see st_accum_note in include/st_hip.h); one thread, plain stores.
 __global__ void accum_note_kernel(const float* __restrict__ sums, const float* d, float* __restrict__ win, float* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const float s = sums[0], n = sums[1];
@@ -49,48 +50,42 @@ __global__ void window_close_kernel(float* __restrict__ win, float* __restrict__
 
 }  // namespace
 
-extern "C" int st2_grad_norm_guard(hipStream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
-                                   float grad_scale, float* guard) {
-  // scratch: as st_grad_norm (st_grad_norm_blocks() + 1 floats, the ticket zero before the first call); same grid, so the same
-  // partial sums and the same merge order
-  if (n <= 0 || (n & 3) || !g || !scratch || !gnorm || !step || !guard) return -1;
+extern "C" int st_grad_norm_blocks(void) { return 1024; }
+
+extern "C" int st_grad_norm(hipStream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
+                            float grad_scale, float* guard, const float* win) {
+  // scratch: st_grad_norm_blocks() + 1 floats, the last one (the ticket) zero before the first call.  One grid for all four
+  // forms, so the same partial sums and the same merge order; guard NULL = no verdict (step, if given, always advances)
+  if (n <= 0 || (n & 3) || !g || !scratch || !gnorm || (!step && (guard || win))) return -1;
   const size_t n4 = (size_t)n / 4;
+  // one workgroup per CU: the tickets are same-address atomics, which serialise (~15 ns each: 1024 workgroups spent 15 us on
+  // them, ce_fwd's 1,200 once 43 us)
   int blocks = (int)((n4 + 1023) / 1024);
   if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(grad_norm_kernel<true>, dim3(blocks), dim3(1024), 0, stream, g, n4, scratch,
-                     reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard, (const float*)nullptr);
+#define ST_NORM_LAUNCH(...)                                                                                          \
+  hipLaunchKernelGGL((grad_norm_kernel<__VA_ARGS__>), dim3(blocks), dim3(1024), 0, stream, g, n4, scratch,                \
+                     reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard, win)
+  if (win) {
+    if (guard) ST_NORM_LAUNCH(true, true);
+    else ST_NORM_LAUNCH(false, true);
+  } else {
+    if (guard) ST_NORM_LAUNCH(true);
+    else ST_NORM_LAUNCH(false);
+  }
+#undef ST_NORM_LAUNCH
   ST_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int st2_grad_norm_win(hipStream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
-                                 float grad_scale, float* guard, const float* win) {
-  // st2_grad_norm_guard's geometry: same partial sums, same merge order; guard NULL = no verdict (step always advances)
-  if (n <= 0 || (n & 3) || !g || !scratch || !gnorm || !step || !win) return -1;
-  const size_t n4 = (size_t)n / 4;
-  int blocks = (int)((n4 + 1023) / 1024);
-  if (blocks > 256) blocks = 256;
-  if (guard)
-    hipLaunchKernelGGL((grad_norm_kernel<true, true>), dim3(blocks), dim3(1024), 0, stream, g, n4, scratch,
-                       reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard, win);
-  else
-    hipLaunchKernelGGL((grad_norm_kernel<false, true>), dim3(blocks), dim3(1024), 0, stream, g, n4, scratch,
-                       reinterpret_cast<unsigned*>(scratch + 1024), gnorm, step, grad_scale, guard, win);
-  ST_CHECK_LAUNCH();
-  return 0;
-}
-
-namespace {
-
-// the shared launcher of st2_adam_clip_avg (win NULL) and st2_adam_clip_win
-int adam_clip_launch(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr, const float* step,
-                     const float* gnorm, float max_norm, float beta1, float beta2, float eps, float grad_scale,
-                     const float* found_inf, float* avg, float decay, int decay_warmup, const float* win) {
+extern "C" int st_adam_clip(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
+                            const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
+                            float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup,
+                            const float* win) {
   if (n <= 0) return 0;
   if ((n & 3) || !p || !g || !m || !v || !lr || !step) return -1;
   if (avg && !(decay >= 0.0f && decay <= 1.0f)) return -1;
   const size_t n4 = (size_t)n / 4;
-  int blocks = (int)((n4 + 255) / 256);      // st_adam_clip's geometry
+  int blocks = (int)((n4 + 255) / 256);
   if (blocks > 4096) blocks = 4096;
 #define ST_ADAM_LAUNCH(GUARD, AVG, WIN)                                                                                      \
   hipLaunchKernelGGL((adam_clip_kernel<GUARD, AVG, WIN>), dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, lr, step, gnorm, \
@@ -111,39 +106,21 @@ int adam_clip_launch(hipStream_t stream, long long n, float* p, float* g, float*
   return 0;
 }
 
-}  // namespace
-
-extern "C" int st2_adam_clip_avg(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
-                                 const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
-                                 float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup) {
-  return adam_clip_launch(stream, n, p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale, found_inf, avg, decay,
-                          decay_warmup, nullptr);
-}
-
-extern "C" int st2_adam_clip_win(hipStream_t stream, long long n, float* p, float* g, float* m, float* v, const float* lr,
-                                 const float* step, const float* gnorm, float max_norm, float beta1, float beta2, float eps,
-                                 float grad_scale, const float* found_inf, float* avg, float decay, int decay_warmup,
-                                 const float* win) {
-  if (!win) return -1;
-  return adam_clip_launch(stream, n, p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale, found_inf, avg, decay,
-                          decay_warmup, win);
-}
-
-extern "C" int st2_accum_note(hipStream_t stream, const float* sums, const float* d, float* win, float* out) {
+extern "C" int st_accum_note(hipStream_t stream, const float* sums, const float* d, float* win, float* out) {
   if (!sums || !win || !out) return -1;
   hipLaunchKernelGGL(accum_note_kernel, dim3(1), dim3(64), 0, stream, sums, d, win, out);
   ST_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int st2_window_close(hipStream_t stream, float* win, float* out) {
+extern "C" int st_window_close(hipStream_t stream, float* win, float* out) {
   if (!win || !out) return -1;
   hipLaunchKernelGGL(window_close_kernel, dim3(1), dim3(64), 0, stream, win, out);
   ST_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int st2_swap_f32(hipStream_t stream, float* a, float* b, long long n) {
+extern "C" int st_swap_f32(hipStream_t stream, float* a, float* b, long long n) {
   if (n <= 0) return 0;
   if ((n & 3) || !a || !b || ((size_t)a & 15) || ((size_t)b & 15)) return -1;
   const float *lo = a < b ? a : b, *hi = a < b ? b : a;

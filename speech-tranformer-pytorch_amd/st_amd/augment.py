@@ -2,9 +2,9 @@
 
 A policy object holds the mask counts and widths; the masks themselves are drawn ON THE DEVICE, per utterance, from the
 same seed in device memory that gives dropout fresh masks on every replay of a captured step (st_amd/rng.py), by one small
-plan launch (st2_specaug_plan), and applied by the kernel that turns the features into bf16 rows anyway (st2_pack_rows_aug
-for the padded inputs of a step, st2_feat_stack_aug for raw features) - no extra pass over the features and nothing on the
-host.  include/st_hip.h (st2_ section) spells the draw out; tests/_specaug_ref.py restates it in Python integers.
+plan launch (st_specaug_plan), and applied by the kernel that turns the features into bf16 rows anyway (st_pack_rows_aug
+for the padded inputs of a step, st_feat_stack_aug for raw features) - no extra pass over the features and nothing on the
+host.  include/st_hip.h (st_specaug_plan) spells the draw out; tests/_specaug_ref.py restates it in Python integers.
 
     enc = model.encoder
     enc.spec_augment = SpecAugment(mel_bins=80, left=3, right=0, frame_rate=30)   # how the step's inputs were stacked

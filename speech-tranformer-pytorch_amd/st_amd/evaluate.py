@@ -3,8 +3,8 @@
 What a recipe reports per epoch - and picks checkpoints, stops early and chooses between raw and averaged weights by - is the
 criterion's value, the plain token-mean NLL (perplexity) and the share of positions whose arg-max is the ground truth, all
 under teacher forcing.  ``EvalStep`` computes them the way ``TrainStep`` computes a step: ``model.forward_packed`` leaves the
-logits in the ragged ``[rows, v_pad]`` layout, ``st3_ce_eval_fwd`` reads every row once (loss numerator, NLL, arg-max hit) and
-``st3_eval_note`` adds the batch into an fp64 accumulator in device memory.  Nothing is scattered to ``[B, L, V]``, nothing is
+logits in the ragged ``[rows, v_pad]`` layout, ``st_ce_eval_fwd`` reads every row once (loss numerator, NLL, arg-max hit) and
+``st_eval_note`` adds the batch into an fp64 accumulator in device memory.  Nothing is scattered to ``[B, L, V]``, nothing is
 saved for a backward, the optimizer and the dropout seed are never touched, and the host reads ONE tensor per pass::
 
     ev = EvalStep(model, vocab_size, criterion=None, use_graph=True, bucket=(T_cap, L_cap), bucket_rows=None)
@@ -48,7 +48,7 @@ class EvalStep:
         (``TrainStep`` documents both).  The first ``graph_warmup`` batches of a bucket run eagerly.
 
         The model must be in ``eval()`` mode - every module of it: a call with dropout or SpecAugment live raises RuntimeError.
-        ``self.acc``: fp64 [8] on the device (st3_eval_note lists the slots), ``self.last``: f32 [4] = the last batch's
+        ``self.acc``: fp64 [8] on the device (st_eval_note lists the slots), ``self.last``: f32 [4] = the last batch's
         (loss, nll, accuracy, tokens).  A target outside the vocabulary that is not PAD does not abort anything: its row is
         left out and counted in ``bad_targets``."""
         if not hasattr(model, "forward_packed"):

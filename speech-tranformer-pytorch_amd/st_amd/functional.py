@@ -1224,7 +1224,7 @@ class VocabFn(torch.autograd.Function):
 
 
 class CeSpec(collections.namedtuple("CeSpec", "confidence smooth zero_col norm")):
-    """A smoothed cross-entropy the HIP kernels run (stx_ce_smooth_fwd / stx_ce_smooth_bwd): the target distribution of a row
+    """A smoothed cross-entropy the HIP kernels run (st_ce_smooth_fwd / st_ce_smooth_bwd): the target distribution of a row
     with target t is ``confidence`` at t, 0 at column ``zero_col`` (-1: none), ``smooth`` everywhere else; ``norm`` names
     the denominator D of the loss - "tokens": the non-ignored rows (counted by the kernel), "rows": every row of the padded,
     batch-trimmed [B, L] layout (the step drivers keep B * L in a device scalar), "sum": D = 1."""
@@ -1297,7 +1297,7 @@ class VocabCeFn(torch.autograd.Function):
     would cast it to the logits' fp32 and VocabFn back to bf16: two more passes over [rows, V]).
 
     spec (a CeSpec, see ce_spec) / denom (its denominator: a 1-element f32 device tensor, read at kernel time): the loss
-    against the smoothed target instead (stx_ce_smooth_fwd / _bwd); None keeps the plain launches.  The plain token-mean NLL of
+    against the smoothed target instead (st_ce_smooth_fwd / _bwd); None keeps the plain launches.  The plain token-mean NLL of
     the call (the loss itself without a spec) is left in ``mod._st_ce_nll``, a device scalar."""
 
     @staticmethod

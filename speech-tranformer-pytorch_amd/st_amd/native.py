@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
+import zlib
 from typing import Optional
 
 import torch
@@ -38,14 +39,17 @@ def _argtypes(name: str, params: str):
     return argtypes
 
 
+def _declarations(text: str):
+    """(name, parameter list) of every ``int st_*(...);`` declaration of the header text, in header order, comments removed."""
+    return re.findall(r"\bint\s+(st_\w+)\s*\(([^)]*)\)\s*;", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
 def parse_header(text: str):
     """-> (SIGNATURES: name -> argtypes of every ``int st_*(...);`` declaration, ABI version, the ST_EPI_* enum) of the text
     of include/st_hip.h.  The header's C subset is tiny: a parameter with a ``*`` or of type st_stream_t is a pointer, the five
     scalar types above are themselves, and ANY other type raises - a new type in the header is a decision, not a default."""
+    sigs = {name: _argtypes(name, params) for name, params in _declarations(text)}
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    sigs = {}
-    for name, params in re.findall(r"\bint\s+(st_\w+)\s*\(([^)]*)\)\s*;", text):
-        sigs[name] = _argtypes(name, params)
     version = re.search(r"#define\s+ST_ABI_VERSION\s+(\d+)", text)
     epi = {k: int(v) for k, v in re.findall(r"\b(ST_EPI_\w+)\s*=\s*(\d+)", text)}
     if not sigs or version is None or len(epi) != 8:
@@ -53,17 +57,28 @@ def parse_header(text: str):
     return sigs, int(version.group(1)), epi
 
 
-def parse_extension(text: str, prefix: str = "stx"):
-    """-> (name -> argtypes of every ``int <prefix>_*(...);`` declaration, <PREFIX>_VERSION) of one of the header's extension
-    sections: the entry points added after the base ABI was frozen (the sections' comments in include/st_hip.h say why they
-    are kept apart).  Same parameter rules as parse_header."""
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    sigs = {name: _argtypes(name, params)
-            for name, params in re.findall(r"\bint\s+(%s_\w+)\s*\(([^)]*)\)\s*;" % re.escape(prefix), text)}
-    version = re.search(r"#define\s+%s_VERSION\s+(\d+)" % re.escape(prefix.upper()), text)
-    if not sigs or version is None:
-        raise RuntimeError("include/st_hip.h: no %s_* declarations / %s_VERSION found: broken checkout" % (prefix, prefix.upper()))
-    return sigs, int(version.group(1))
+def abi_fingerprint(text: str) -> int:
+    """What ST_ABI_VERSION must be for this header text: a CRC of the ABI itself.  One line ``NAME(T1,...,Tn)`` per declaration
+    in header order - Ti the parameter without ``const``, its name and all whitespace (``const void* const* X`` -> ``void**``,
+    ``long long n`` -> ``longlong``, ``(void)`` -> no parameter) - then one line ``NAME=VALUE`` per ST_EPI_* enumerator.
+    Comments, layout, parameter names and const-ness do not count; a type, a parameter, a declaration, their order do."""
+    lines = []
+    for name, params in _declarations(text):
+        types = [re.sub(r"\s+", "", re.sub(r"\w+\s*$", "", re.sub(r"\bconst\b", " ", p)))
+                 for p in ([] if params.strip() == "void" else params.split(","))]
+        lines.append("%s(%s)" % (name, ",".join(types)))
+    lines += ["%s=%s" % kv for kv in re.findall(r"\b(ST_EPI_\w+)\s*=\s*(\d+)", re.sub(r"/\*.*?\*/", "", text, flags=re.S))]
+    return zlib.crc32("\n".join(lines).encode("utf-8")) & 0x7fffffff
+
+
+def check_fingerprint(text: str) -> int:
+    """The header's ST_ABI_VERSION literal, which must BE the fingerprint of its declarations - or the RuntimeError that names
+    the number to write (a declaration was edited; the literal is what st_version() and a C consumer see)."""
+    literal, want = parse_header(text)[1], abi_fingerprint(text)
+    if literal != want:
+        raise RuntimeError("include/st_hip.h: ST_ABI_VERSION is %d but its declarations have the fingerprint %d: a declaration "
+                           "changed - write `#define ST_ABI_VERSION %d` and rebuild (python __graft_entry__.py)" % (literal, want, want))
+    return literal
 
 
 def _read_header() -> str:
@@ -78,12 +93,7 @@ def _read_header() -> str:
 # name -> argtypes (restype is int everywhere), the library's ABI version and st_gemm's epilogue selectors: all read from
 # include/st_hip.h, the one place they are written down
 SIGNATURES, ABI_VERSION, _EPI = parse_header(_read_header())
-# ... and the same for the header's extension section (the stx_* entry points)
-EXT_SIGNATURES, EXT_VERSION = parse_extension(_read_header())
-# ... and its second extension section (st2_*: SpecAugment, the optimizer's options, gradient accumulation)
-EXT2_SIGNATURES, EXT2_VERSION = parse_extension(_read_header(), "st2")
-# ... and its third (st3_*: forward-only validation)
-EXT3_SIGNATURES, EXT3_VERSION = parse_extension(_read_header(), "st3")
+check_fingerprint(_read_header())      # ... where the version is a fingerprint of the declarations, so an edited one cannot keep it
 (EPI_BF16, EPI_BF16_RELU, EPI_F32, EPI_BF16_MASK, EPI_BF16_ADD, EPI_F32_ATOMIC, EPI_F32_ATOMIC_T, EPI_BF16_DELTA) = (
     _EPI["ST_" + k] for k in ("EPI_BF16", "EPI_BF16_RELU", "EPI_F32", "EPI_BF16_MASK", "EPI_BF16_ADD", "EPI_F32_ATOMIC",
                               "EPI_F32_ATOMIC_T", "EPI_BF16_DELTA"))
@@ -186,23 +196,11 @@ def load(build_if_missing: bool = True):
     if ver != ABI_VERSION:
         raise RuntimeError("libst_hip.so at %s has ABI version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
                            % (path, ver, ABI_VERSION))
-    for entry, want, what in (("stx_version", EXT_VERSION, "extension"), ("st2_version", EXT2_VERSION, "second extension"),
-                              ("st3_version", EXT3_VERSION, "third extension")):
-        try:
-            getattr(cdll, entry).restype = _c_int
-            xver = int(getattr(cdll, entry)())
-        except AttributeError:
-            xver = -1
-        if xver != want:
-            raise RuntimeError("libst_hip.so at %s has %s version %d, this binding needs %d: rebuild it (python __graft_entry__.py)"
-                               % (path, what, xver, want))
-    bound = (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT2_SIGNATURES.items())
-             + list(EXT3_SIGNATURES.items()))
-    missing = [name for name, _ in bound if not hasattr(cdll, name)]
+    missing = [name for name in SIGNATURES if not hasattr(cdll, name)]
     if missing:
         raise RuntimeError("libst_hip.so at %s lacks %s: rebuild it (python __graft_entry__.py)" % (path, ", ".join(missing)))
     lib = _Lib()
-    for name, argtypes in bound:
+    for name, argtypes in SIGNATURES.items():
         fn = getattr(cdll, name)
         fn.argtypes = argtypes
         fn.restype = _c_int
@@ -1201,7 +1199,7 @@ def _specaug_args(who, n_time, n_freq, left, right, interval):
 
 def specaug_plan(seed, salt, length, table, n_time, time_width, time_ratio_permille, n_freq, freq_width, mel_bins, interval=1,
                  right=0):
-    """SpecAugment's masks of one step (st2_specaug_plan): table int32 [B, n_time + n_freq, 2] <- (start, width) of every
+    """SpecAugment's masks of one step (st_specaug_plan): table int32 [B, n_time + n_freq, 2] <- (start, width) of every
     mask, drawn from the device seed (the 1-element int32 tensor of st_amd.rng) and ``salt``.  length: int32 [B] on the device
     - raw frames with (interval 1, right 0), else rows already stacked with that geometry."""
     B = length.numel()
@@ -1214,14 +1212,14 @@ def specaug_plan(seed, salt, length, table, n_time, time_width, time_ratio_permi
     _dev(table, I32, (B, n_time + n_freq, 2), "specaug_plan: table")
     _dev(seed, I32, (1,), "specaug_plan: seed"), _vec(length, I32, B, "specaug_plan: length")
     _tag("specaug_plan", B, n_time + n_freq, io=(length, table))
-    _check(load().st2_specaug_plan(_stream(), seed.data_ptr(), int(salt) & 0xFFFFFFFF, length.data_ptr(), B, interval, right, n_time,
-                                   int(time_width), int(time_ratio_permille), n_freq, int(freq_width), int(mel_bins),
-                                   table.data_ptr()), "st2_specaug_plan")
+    _check(load().st_specaug_plan(_stream(), seed.data_ptr(), int(salt) & 0xFFFFFFFF, length.data_ptr(), B, interval, right, n_time,
+                                  int(time_width), int(time_ratio_permille), n_freq, int(freq_width), int(mel_bins),
+                                  table.data_ptr()), "st_specaug_plan")
     return table
 
 
 def pack_rows_aug(x, off, length, out, table, n_time, n_freq, mel_bins, left=0, right=0, interval=1):
-    """pack_rows with the masks of ``table`` applied (st2_pack_rows_aug): x fp32 [B, T, mel_bins * (1 + left + right)], rows
+    """pack_rows with the masks of ``table`` applied (st_pack_rows_aug): x fp32 [B, T, mel_bins * (1 + left + right)], rows
     already stacked / subsampled with that geometry."""
     if x.dim() != 3:
         raise ValueError("pack_rows_aug: x must be [B, T, F], got %s" % (tuple(x.shape),))
@@ -1239,14 +1237,14 @@ def pack_rows_aug(x, off, length, out, table, n_time, n_freq, mel_bins, left=0, 
         raise ValueError("pack_rows_aug: off / len must have one entry per utterance (%d)" % B)
     _mat(out, BF16, "out", ld=Fd)
     _tag("pack_rows_aug", out.shape[0], Fd, io=(float(out.shape[0]) * Fd * x.element_size(), out, table))
-    _check(load().st2_pack_rows_aug(_stream(), x.data_ptr(), B, T, Fd, off.data_ptr(), length.data_ptr(), out.data_ptr(),
-                                    table.data_ptr(), n_time, n_freq, mel_bins, left, right, interval), "st2_pack_rows_aug")
+    _check(load().st_pack_rows_aug(_stream(), x.data_ptr(), B, T, Fd, off.data_ptr(), length.data_ptr(), out.data_ptr(),
+                                   table.data_ptr(), n_time, n_freq, mel_bins, left, right, interval), "st_pack_rows_aug")
     return out
 
 
 def feat_stack_aug(x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out, table, n_time, n_freq):
     """feat_stack with the masks of ``table`` (planned with the raw lengths) applied after CMVN, before stacking
-    (st2_feat_stack_aug)."""
+    (st_feat_stack_aug)."""
     if x.dim() != 3:
         raise ValueError("feat_stack_aug: x must be [B, T, F], got %s" % (tuple(x.shape),))
     B, T, F = x.shape
@@ -1260,10 +1258,10 @@ def feat_stack_aug(x, in_len, stats, left, right, interval, out_off, out_len, ma
     if stats is not None:
         _dev(stats, F32, (B, 2, F + 1), "feat_stack_aug: stats")
     _tag("feat_stack_aug", B, T, F)
-    rc = load().st2_feat_stack_aug(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), left, right, interval,
-                                   out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(), out.stride(0),
-                                   table.data_ptr(), n_time, n_freq)
-    _check(rc, "st2_feat_stack_aug")
+    rc = load().st_feat_stack_aug(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), left, right, interval,
+                                  out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(), out.stride(0),
+                                  table.data_ptr(), n_time, n_freq)
+    _check(rc, "st_feat_stack_aug")
     return out
 
 
@@ -1548,29 +1546,29 @@ def _ce_smooth_args(who, logits, target, V, index, zero_col, denom, lse, sums):
 
 def ce_smooth_fwd(logits, target, ignore_index, confidence, smooth, zero_col, lse, sums, V=None, index=None, denom=None):
     """Cross-entropy against the smoothed target (confidence at the target, 0 at zero_col, smooth elsewhere) - see
-    stx_ce_smooth_fwd.  V: the TRUE vocabulary size (padding columns of ``logits`` are not read); sums f32 [4] = (sum of the row
+    st_ce_smooth_fwd.  V: the TRUE vocabulary size (padding columns of ``logits`` are not read); sums f32 [4] = (sum of the row
     losses, non-ignored rows, the loss = sum / (*denom, or the row count when denom is None), the plain token-mean NLL)."""
     R, V = _ce_smooth_args("ce_smooth_fwd", logits, target, V, index, zero_col, denom, lse, sums)
     row_loss = torch.empty(R, dtype=F32, device=logits.device)       # scratch: summed by the call's second launch
     _tag("ce_smooth_fwd", R, V, 0, io=(2.0 * R * V, 8.0 * R))
-    _check(load().stx_ce_smooth_fwd(_stream(), logits.data_ptr(), logits.stride(0), R, V, target.data_ptr(), _p(index),
-                                    int(ignore_index), float(confidence), float(smooth), int(zero_col), _p(denom), lse.data_ptr(),
-                                    row_loss.data_ptr(), sums.data_ptr()), "stx_ce_smooth_fwd")
+    _check(load().st_ce_smooth_fwd(_stream(), logits.data_ptr(), logits.stride(0), R, V, target.data_ptr(), _p(index),
+                                   int(ignore_index), float(confidence), float(smooth), int(zero_col), _p(denom), lse.data_ptr(),
+                                   row_loss.data_ptr(), sums.data_ptr()), "st_ce_smooth_fwd")
 
 
 def ce_smooth_bwd(logits, target, ignore_index, confidence, smooth, zero_col, lse, sums, grad_out, dlogits, V=None, index=None,
                   denom=None):
-    """dlogits (bf16, same rows as logits) = d(loss) / d(logits) * grad_out for ce_smooth_fwd's loss - see stx_ce_smooth_bwd."""
+    """dlogits (bf16, same rows as logits) = d(loss) / d(logits) * grad_out for ce_smooth_fwd's loss - see st_ce_smooth_bwd."""
     R, V = _ce_smooth_args("ce_smooth_bwd", logits, target, V, index, zero_col, denom, lse, sums)
     _mat(dlogits, BF16, "dlogits", rows=R, ld=dlogits.shape[-1])
     if dlogits.shape[1] < V or dlogits.stride(0) % 8:
         raise ValueError("ce_smooth_bwd: dlogits must be a contiguous bf16 [R, >= V] matrix with a row length that is a multiple of 8")
     _vec(grad_out, F32, 1, "grad_out")
     _tag("ce_smooth_bwd", R, V, 0, io=(4.0 * R * V, 8.0 * R))
-    _check(load().stx_ce_smooth_bwd(_stream(), logits.data_ptr(), logits.stride(0), R, V, target.data_ptr(), _p(index),
-                                    int(ignore_index), float(confidence), float(smooth), int(zero_col), _p(denom), lse.data_ptr(),
-                                    sums.data_ptr(), grad_out.data_ptr(), dlogits.data_ptr(), dlogits.stride(0)),
-           "stx_ce_smooth_bwd")
+    _check(load().st_ce_smooth_bwd(_stream(), logits.data_ptr(), logits.stride(0), R, V, target.data_ptr(), _p(index),
+                                   int(ignore_index), float(confidence), float(smooth), int(zero_col), _p(denom), lse.data_ptr(),
+                                   sums.data_ptr(), grad_out.data_ptr(), dlogits.data_ptr(), dlogits.stride(0)),
+           "st_ce_smooth_bwd")
 
 
 def zero_tails(table, n_max):
@@ -1607,20 +1605,49 @@ def grad_norm_scratch(device):
     return torch.zeros(_norm_blocks() + 1, dtype=F32, device=device)
 
 
+def _scalars(who, *pairs):
+    for t, nm in pairs:
+        if t is not None and not (t.is_cuda and t.dtype == F32 and t.numel() == 1):
+            raise ValueError("%s: %s must be an fp32 scalar on the GPU" % (who, nm))
+
+
+def _grad_norm(who, g, scratch, out, step, guard, win, grad_scale):
+    """st_grad_norm for the three wrappers below: ``who`` names the wrapper in messages and labels the launch for bench.py."""
+    _vec(g, F32, 0, who + ": g")
+    if g.numel() % 4:
+        raise ValueError("%s: g must hold a multiple of 4 elements" % who)
+    _vec(scratch, F32, _norm_blocks() + 1, "scratch")
+    _scalars(who, (out, "out"), (step, "step"))
+    if guard is not None:
+        _dev(guard, F32, (2,), who + ": guard")
+    if win is not None:
+        _dev(win, F32, (4,), who + ": win")
+    _tag(who, g.numel(), io=(4.0 * g.numel(),))
+    _check(load().st_grad_norm(_stream(), g.data_ptr(), g.numel(), scratch.data_ptr(), out.data_ptr(), _p(step), float(grad_scale),
+                               _p(guard), _p(win)), "st_grad_norm")
+    return out
+
+
 def grad_norm(g, scratch, out, step=None, grad_scale=1.0):
     """out (fp32 scalar tensor) = grad_scale * ||g||_2 over the flat fp32 buffer g; step (fp32 scalar tensor, optional) += 1 -
     see st_grad_norm."""
-    _vec(g, F32, 0, "grad_norm: g")
-    if g.numel() % 4:
-        raise ValueError("grad_norm: g must hold a multiple of 4 elements")
-    _vec(scratch, F32, _norm_blocks() + 1, "scratch")
-    for t, nm in ((out, "out"), (step, "step")):
-        if t is not None and not (t.is_cuda and t.dtype == F32 and t.numel() == 1):
-            raise ValueError("grad_norm: %s must be an fp32 scalar on the GPU" % nm)
-    _tag("grad_norm", g.numel(), io=(4.0 * g.numel(),))
-    _check(load().st_grad_norm(_stream(), g.data_ptr(), g.numel(), scratch.data_ptr(), out.data_ptr(), _p(step), float(grad_scale)),
-           "st_grad_norm")
-    return out
+    return _grad_norm("grad_norm", g, scratch, out, step, None, None, grad_scale)
+
+
+def grad_norm_guard(g, scratch, out, step, guard, grad_scale=1.0):
+    """grad_norm with a verdict (st_grad_norm's guard): out = grad_scale * ||g||_2; a finite norm advances ``step`` and clears
+    guard[0], a non-finite one leaves ``step`` alone, sets guard[0] = 1 and counts up guard[1].  guard: fp32 [2] on the GPU."""
+    if step is None or guard is None:
+        raise ValueError("grad_norm_guard: step and guard are required")
+    return _grad_norm("grad_norm_guard", g, scratch, out, step, guard, None, grad_scale)
+
+
+def grad_norm_win(g, scratch, out, step, guard, win, grad_scale=1.0):
+    """grad_norm_guard over a window (st_grad_norm's win): out = grad_scale * ||g||_2 / win[0]; guard (fp32 [2]) may be None -
+    then ``step`` always advances; with a guard a denominator win[0] <= 0 is a bad verdict as well."""
+    if step is None or win is None:
+        raise ValueError("grad_norm_win: step and win are required")
+    return _grad_norm("grad_norm_win", g, scratch, out, step, guard, win, grad_scale)
 
 
 def cast_bf16(src, dst):
@@ -1632,65 +1659,54 @@ def cast_bf16(src, dst):
     return dst
 
 
-def adam_clip(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale=1.0):
-    """In place: g *= grad_scale * min(1, max_norm / (gnorm + 1e-6)); (p, m, v) <- Adam(p, g, m, v; lr, step).  lr / step /
-    gnorm are 0-dim fp32 device tensors (gnorm None: no clipping); grad_scale: see st_adam_clip (1 / world behind a summing
-    all-reduce)."""
-    n = p.numel()
-    for t, k, nm in ((p, n, "p"), (g, n, "g"), (m, n, "m"), (v, n, "v"), (lr, 1, "lr"), (step, 1, "step"), (gnorm, 1, "gnorm")):
-        _vec(t, F32, k, nm)
-        if t is not None and t.numel() != k:
-            raise ValueError("adam_clip: %s holds %d elements, expected %d" % (nm, t.numel(), k))
-    _tag("adam_clip", p.numel(), io=(32.0 * p.numel(),))      # p, g, m, v read; p, m, v written; g zeroed (fp32)
-    _check(load().st_adam_clip(_stream(), p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(),
-                               step.data_ptr(), _p(gnorm), float(max_norm), float(beta1), float(beta2), float(eps),
-                               float(grad_scale)), "st_adam_clip")
-
-
-def _scalars(who, *pairs):
-    for t, nm in pairs:
-        if t is not None and not (t.is_cuda and t.dtype == F32 and t.numel() == 1):
-            raise ValueError("%s: %s must be an fp32 scalar on the GPU" % (who, nm))
-
-
-def grad_norm_guard(g, scratch, out, step, guard, grad_scale=1.0):
-    """grad_norm with a verdict (st2_grad_norm_guard): out = grad_scale * ||g||_2; a finite norm advances ``step`` and clears
-    guard[0], a non-finite one leaves ``step`` alone, sets guard[0] = 1 and counts up guard[1].  guard: fp32 [2] on the GPU."""
-    _vec(g, F32, 0, "grad_norm_guard: g")
-    if g.numel() % 4:
-        raise ValueError("grad_norm_guard: g must hold a multiple of 4 elements")
-    _vec(scratch, F32, _norm_blocks() + 1, "scratch")
-    if step is None or guard is None:
-        raise ValueError("grad_norm_guard: step and guard are required")
-    _scalars("grad_norm_guard", (out, "out"), (step, "step"))
-    _dev(guard, F32, (2,), "grad_norm_guard: guard")
-    _tag("grad_norm_guard", g.numel(), io=(4.0 * g.numel(),))
-    _check(load().st2_grad_norm_guard(_stream(), g.data_ptr(), g.numel(), scratch.data_ptr(), out.data_ptr(), step.data_ptr(),
-                                      float(grad_scale), guard.data_ptr()), "st2_grad_norm_guard")
-    return out
-
-
-def adam_clip_avg(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale=1.0, found_inf=None, avg=None,
-                  decay=0.999, decay_warmup=True):
-    """adam_clip plus (st2_adam_clip_avg): found_inf (fp32 device scalar or None) - non-zero: nothing is written; avg (fp32 [n] or
-    None) - avg += w * (p_new - avg), w = 1 - decay, or with decay_warmup 1 - min(decay, (1 + step) / (10 + step))."""
+def _adam_clip(who, p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale, found_inf, avg, decay, decay_warmup, win):
+    """st_adam_clip for the three wrappers below: ``who`` names the wrapper in messages and labels the launch for bench.py."""
     n = p.numel()
     for t, k, nm in ((p, n, "p"), (g, n, "g"), (m, n, "m"), (v, n, "v"), (lr, 1, "lr"), (step, 1, "step"), (gnorm, 1, "gnorm"),
                      (found_inf, 1, "found_inf"), (avg, n, "avg")):
         _vec(t, F32, k, nm)
         if t is not None and t.numel() != k:
-            raise ValueError("adam_clip_avg: %s holds %d elements, expected %d" % (nm, t.numel(), k))
+            raise ValueError("%s: %s holds %d elements, expected %d" % (who, nm, t.numel(), k))
+    if win is not None:
+        _dev(win, F32, (4,), who + ": win")
+    if n % 4:
+        raise ValueError("%s: the buffers must hold a multiple of 4 elements" % who)
     if avg is not None and not 0.0 <= float(decay) <= 1.0:
-        raise ValueError("adam_clip_avg: decay must lie in [0, 1], got %r" % (decay,))
-    _tag("adam_clip_avg", n, io=((32.0 if avg is None else 40.0) * n,))      # adam_clip's streams + avg read and written
-    _check(load().st2_adam_clip_avg(_stream(), n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(),
-                                    step.data_ptr(), _p(gnorm), float(max_norm), float(beta1), float(beta2), float(eps),
-                                    float(grad_scale), _p(found_inf), _p(avg), float(decay), int(bool(decay_warmup))),
-           "st2_adam_clip_avg")
+        raise ValueError("%s: decay must lie in [0, 1], got %r" % (who, decay))
+    _tag(who, n, io=((32.0 if avg is None else 40.0) * n,))      # p, g, m, v read; p, m, v, g written (fp32); + avg read and written
+    _check(load().st_adam_clip(_stream(), n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(),
+                               step.data_ptr(), _p(gnorm), float(max_norm), float(beta1), float(beta2), float(eps),
+                               float(grad_scale), _p(found_inf), _p(avg), float(decay), int(bool(decay_warmup)), _p(win)),
+           "st_adam_clip")
+
+
+def adam_clip(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale=1.0):
+    """In place: g *= grad_scale * min(1, max_norm / (gnorm + 1e-6)); (p, m, v) <- Adam(p, g, m, v; lr, step).  lr / step /
+    gnorm are 0-dim fp32 device tensors (gnorm None: no clipping); grad_scale: see st_adam_clip (1 / world behind a summing
+    all-reduce)."""
+    _adam_clip("adam_clip", p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale, None, None, 0.0, False, None)
+
+
+def adam_clip_avg(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale=1.0, found_inf=None, avg=None,
+                  decay=0.999, decay_warmup=True):
+    """adam_clip plus (st_adam_clip's found_inf / avg): found_inf (fp32 device scalar or None) - non-zero: nothing is written; avg
+    (fp32 [n] or None) - avg += w * (p_new - avg), w = 1 - decay, or with decay_warmup 1 - min(decay, (1 + step) / (10 + step))."""
+    _adam_clip("adam_clip_avg", p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale, found_inf, avg, decay,
+               decay_warmup, None)
+
+
+def adam_clip_win(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, win, grad_scale=1.0, found_inf=None, avg=None,
+                  decay=0.999, decay_warmup=True):
+    """adam_clip_avg over a window (st_adam_clip's win): the gradient is also divided by win[0] (win: fp32 [4]) and g is left
+    holding ZEROS; under a non-zero found_inf the zeros are all that is written."""
+    if win is None:
+        raise ValueError("adam_clip_win: win is required")
+    _adam_clip("adam_clip_win", p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, grad_scale, found_inf, avg, decay,
+               decay_warmup, win)
 
 
 def swap_(a, b):
-    """Exchange the contents of two fp32 buffers of equal size in place (st2_swap_f32), one launch."""
+    """Exchange the contents of two fp32 buffers of equal size in place (st_swap_f32), one launch."""
     _vec(a, F32, 0, "swap_: a"), _vec(b, F32, a.numel(), "swap_: b")
     if a.numel() != b.numel() or a.numel() % 4:
         raise ValueError("swap_: the buffers must hold the same multiple of 4 elements, got %d and %d" % (a.numel(), b.numel()))
@@ -1700,12 +1716,12 @@ def swap_(a, b):
     if a.numel() and lo + 4 * a.numel() > hi:
         raise ValueError("swap_: the buffers overlap")
     _tag("swap", a.numel(), io=(16.0 * a.numel(),))
-    _check(load().st2_swap_f32(_stream(), a.data_ptr(), b.data_ptr(), a.numel()), "st2_swap_f32")
+    _check(load().st_swap_f32(_stream(), a.data_ptr(), b.data_ptr(), a.numel()), "st_swap_f32")
 
 
-# ---- gradient accumulation over micro-batches: the window's state in device memory (st2_, version 3) -------------------------
+# ---- gradient accumulation over micro-batches: the window's state in device memory ----------------------------------------------
 def accum_note(sums, d, win, out):
-    """One micro-batch joins the window (st2_accum_note): win[1] += sums[0], win[2] += sums[3] * sums[1], win[3] += 1,
+    """One micro-batch joins the window (st_accum_note): win[1] += sums[0], win[2] += sums[3] * sums[1], win[3] += 1,
     win[0] += d (d None: win[0] = 1); out[0] = sums[0] / d, the micro-batch's own loss.  sums: the fp32 [4] of ce_smooth_fwd run
     with a denominator of 1; d: a 1-element fp32 device tensor (a view into sums is fine) or None; win: fp32 [4]."""
     _dev(sums, F32, (4,), "accum_note: sums"), _dev(win, F32, (4,), "accum_note: win")
@@ -1715,65 +1731,22 @@ def accum_note(sums, d, win, out):
     if d is not None and not d.is_contiguous():
         raise ValueError("accum_note: d must be contiguous")
     _tag("accum_note", 1)
-    _check(load().st2_accum_note(_stream(), sums.data_ptr(), _p(d), win.data_ptr(), out.data_ptr()), "st2_accum_note")
+    _check(load().st_accum_note(_stream(), sums.data_ptr(), _p(d), win.data_ptr(), out.data_ptr()), "st_accum_note")
     return out
 
 
 def window_close(win, out):
     """out (fp32 [4]) = (win[1] / win[0], win[2] / win[0], win[0], win[3]): the window's loss, plain NLL, denominator and
-    micro-batch count; then win = 0 (st2_window_close)."""
+    micro-batch count; then win = 0 (st_window_close)."""
     _dev(win, F32, (4,), "window_close: win"), _dev(out, F32, (4,), "window_close: out")
     if win.data_ptr() == out.data_ptr():
         raise ValueError("window_close: win and out must be different buffers")
     _tag("window_close", 1)
-    _check(load().st2_window_close(_stream(), win.data_ptr(), out.data_ptr()), "st2_window_close")
+    _check(load().st_window_close(_stream(), win.data_ptr(), out.data_ptr()), "st_window_close")
     return out
 
 
-def grad_norm_win(g, scratch, out, step, guard, win, grad_scale=1.0):
-    """grad_norm_guard over a window (st2_grad_norm_win): out = grad_scale * ||g||_2 / win[0]; guard (fp32 [2]) may be None -
-    then ``step`` always advances; with a guard a denominator win[0] <= 0 is a bad verdict as well."""
-    if step is None or win is None:
-        raise ValueError("grad_norm_win: step and win are required")
-    _vec(g, F32, 0, "grad_norm_win: g")
-    if g.numel() == 0 or g.numel() % 4:
-        raise ValueError("grad_norm_win: g must hold a positive multiple of 4 elements")
-    _vec(scratch, F32, _norm_blocks() + 1, "scratch")
-    _scalars("grad_norm_win", (out, "out"), (step, "step"))
-    if guard is not None:
-        _dev(guard, F32, (2,), "grad_norm_win: guard")
-    _dev(win, F32, (4,), "grad_norm_win: win")
-    _tag("grad_norm_win", g.numel(), io=(4.0 * g.numel(),))
-    _check(load().st2_grad_norm_win(_stream(), g.data_ptr(), g.numel(), scratch.data_ptr(), out.data_ptr(), step.data_ptr(),
-                                    float(grad_scale), _p(guard), win.data_ptr()), "st2_grad_norm_win")
-    return out
-
-
-def adam_clip_win(p, g, m, v, lr, step, gnorm, max_norm, beta1, beta2, eps, win, grad_scale=1.0, found_inf=None, avg=None,
-                  decay=0.999, decay_warmup=True):
-    """adam_clip_avg over a window (st2_adam_clip_win): the gradient is also divided by win[0] (win: fp32 [4]) and g is left
-    holding ZEROS; under a non-zero found_inf the zeros are all that is written."""
-    if win is None:
-        raise ValueError("adam_clip_win: win is required")
-    n = p.numel()
-    for t, k, nm in ((p, n, "p"), (g, n, "g"), (m, n, "m"), (v, n, "v"), (lr, 1, "lr"), (step, 1, "step"), (gnorm, 1, "gnorm"),
-                     (found_inf, 1, "found_inf"), (avg, n, "avg")):
-        _vec(t, F32, k, nm)
-        if t is not None and t.numel() != k:
-            raise ValueError("adam_clip_win: %s holds %d elements, expected %d" % (nm, t.numel(), k))
-    _dev(win, F32, (4,), "adam_clip_win: win")
-    if n % 4:
-        raise ValueError("adam_clip_win: the buffers must hold a multiple of 4 elements")
-    if avg is not None and not 0.0 <= float(decay) <= 1.0:
-        raise ValueError("adam_clip_win: decay must lie in [0, 1], got %r" % (decay,))
-    _tag("adam_clip_win", n, io=((32.0 if avg is None else 40.0) * n,))
-    _check(load().st2_adam_clip_win(_stream(), n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(),
-                                    step.data_ptr(), _p(gnorm), float(max_norm), float(beta1), float(beta2), float(eps),
-                                    float(grad_scale), _p(found_inf), _p(avg), float(decay), int(bool(decay_warmup)),
-                                    win.data_ptr()), "st2_adam_clip_win")
-
-
-# ---- forward-only validation: per-row loss / NLL / arg-max hit and the epoch accumulator (st3_, version 1) -------------------
+# ---- forward-only validation: per-row loss / NLL / arg-max hit and the epoch accumulator ----------------------------------------
 F64 = torch.float64
 
 
@@ -1798,7 +1771,7 @@ def _eval_gpu(who, **tensors):
 
 def ce_eval_fwd(logits, target, ignore_index, confidence, smooth, zero_col, rows, V=None, index=None):
     """rows (f32 [R, 4]) = per logits row {criterion numerator, plain NLL, 1 if the arg-max over the first V columns is the
-    target, state} - see st3_ce_eval_fwd.  logits f32 [R, ldl] with ldl >= V (unit column stride); V: the TRUE vocabulary
+    target, state} - see st_ce_eval_fwd.  logits f32 [R, ldl] with ldl >= V (unit column stride); V: the TRUE vocabulary
     (None: every column); index: row r's target is target.view(-1)[index[r]].  (confidence, smooth, zero_col) as
     ce_smooth_fwd; (1, 0, -1) is the plain loss.  A target outside [0, V) that is not ignore_index is counted, never followed."""
     who = "ce_eval_fwd"
@@ -1817,13 +1790,13 @@ def ce_eval_fwd(logits, target, ignore_index, confidence, smooth, zero_col, rows
     _eval_arg(who, index, I64, (R,), "index", optional=True)
     _eval_gpu(who, logits=logits, target=target, rows=rows, index=index)
     _tag("ce_eval_fwd", R, V, 0, io=(4.0 * R * V, 24.0 * R))
-    _check(load().st3_ce_eval_fwd(_stream(), logits.data_ptr(), ldl, R, V, target.data_ptr(), _p(index), int(ignore_index),
-                                  float(confidence), float(smooth), int(zero_col), rows.data_ptr()), "st3_ce_eval_fwd")
+    _check(load().st_ce_eval_fwd(_stream(), logits.data_ptr(), ldl, R, V, target.data_ptr(), _p(index), int(ignore_index),
+                                 float(confidence), float(smooth), int(zero_col), rows.data_ptr()), "st_ce_eval_fwd")
     return rows
 
 
 def eval_note(rows, acc, last, denom=None):
-    """One batch joins the epoch (st3_eval_note): the rows of ce_eval_fwd are summed in a fixed order in fp64 and ADDED into
+    """One batch joins the epoch (st_eval_note): the rows of ce_eval_fwd are summed in a fixed order in fp64 and ADDED into
     acc (f64 [8]: loss numerator, loss denominator, NLL sum, tokens, hits, batches, stray labels, spare); last (f32 [4]) = this
     batch's (loss, nll, accuracy, tokens).  denom (1-element f32 device tensor or None): the batch's loss denominator instead
     of its token count."""
@@ -1834,7 +1807,7 @@ def eval_note(rows, acc, last, denom=None):
     _eval_arg(who, denom, F32, (1,), "denom", optional=True)
     _eval_gpu(who, rows=rows, acc=acc, last=last, denom=denom)
     _tag("eval_note", rows.shape[0], io=(16.0 * rows.shape[0],))
-    _check(load().st3_eval_note(_stream(), rows.data_ptr(), rows.shape[0], _p(denom), acc.data_ptr(), last.data_ptr()), "st3_eval_note")
+    _check(load().st_eval_note(_stream(), rows.data_ptr(), rows.shape[0], _p(denom), acc.data_ptr(), last.data_ptr()), "st_eval_note")
     return last
 
 

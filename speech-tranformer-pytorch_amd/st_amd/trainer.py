@@ -28,7 +28,7 @@ collectives between them.
 Gradient accumulation (``TrainStep(..., accumulate=K)``): K calls are K micro-batches of ONE update whose objective is what one
 step on their concatenation would compute.  Every micro-batch adds the gradient of its SUM loss into the flat buffer; the
 denominator (the window's token count, say) is summed on the device and applied once, inside the norm and the clip + Adam
-kernels of the update (st2_grad_norm_win, st2_adam_clip_win) - no host read, and the update kernel leaves the buffer zeroed for
+kernels of the update (st_grad_norm, st_adam_clip with their win pointer) - no host read, and the update kernel leaves the buffer zeroed for
 the next window.  In graph mode the micro-batch and the update are two captures.
 """
 from __future__ import annotations
@@ -217,7 +217,7 @@ class TrainStep:
         if self._win is None or self._win.device != device or loads != self._loads:
             if self._win is None or self._win.device != device:
                 self._win = torch.zeros(4, dtype=torch.float32, device=device)        # denominator, loss sum, NLL sum, micro-batches
-                self._win_out = torch.zeros(4, dtype=torch.float32, device=device)    # what st2_window_close leaves
+                self._win_out = torch.zeros(4, dtype=torch.float32, device=device)    # what st_window_close leaves
                 self._ce_denom = torch.ones(1, dtype=torch.float32, device=device)    # the kernels' denominator: always 1
                 self._gnorm = torch.zeros((), dtype=torch.float32, device=device)
                 self.window_loss, self.window_nll = self._win_out[0], self._win_out[1]

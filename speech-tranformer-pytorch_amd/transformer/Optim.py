@@ -177,7 +177,7 @@ class ScheduledOptim(object):
         return self._norm_scratch
 
     def _step_window(self, grad_norm, max_norm, grad_scale, win):
-        """The update of an accumulation window: ``st2_grad_norm_win`` + ``st2_adam_clip_win``.  The flat gradient buffer holds
+        """The update of an accumulation window: ``st_grad_norm`` + ``st_adam_clip`` with their ``win`` pointer.  The flat gradient buffer holds
         the SUM over the window's micro-batches and ``win`` (device f32 [4]) its denominator in win[0]: the norm returned and
         the gradient Adam consumes are those of ``grad_scale * g / win[0]``.  With the guard on, a non-finite norm or a
         denominator <= 0 skips the update.  Either way the gradient buffer holds ZEROS afterwards, not the clipped gradient."""
@@ -211,7 +211,7 @@ class ScheduledOptim(object):
         grad_norm: True = compute it here (returned as a device scalar), or a device scalar already computed.
         grad_scale: the gradient buffer still has to be multiplied by this (st_amd.dp.GradReducer.synchronize(divide=False)
         leaves the rank SUM and returns 1 / world): folded into the norm and the clip coefficient - no pass of its own.
-        With the guard or the average enabled the two launches are ``st2_grad_norm_guard`` and ``st2_adam_clip_avg``; a norm
+        With the guard or the average enabled the two launches are ``st_grad_norm`` with its guard and ``st_adam_clip`` with ``found_inf`` / ``avg``; a norm
         handed in (the joint step) gives the verdict through torch ops on that scalar - no host read either way.
         window: the device f32 [4] state of a gradient-accumulation window - see :meth:`_step_window`."""
         if window is not None:

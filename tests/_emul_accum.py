@@ -1,4 +1,4 @@
-"""Test-only torch emulations of the gradient-accumulation wrappers of st_amd.native's st2_ section (accum_note, window_close,
+"""Test-only torch emulations of the gradient-accumulation wrappers of st_amd.native (accum_note, window_close,
 grad_norm_win, adam_clip_win), like tests/_emul_optim.py: the host logic of TrainStep(accumulate=K) / ScheduledOptim runs on CPU
 tensors against them.  The arithmetic follows include/st_hip.h; it is NOT the kernels' rounding (the -m gpu tests pin that on
 hardware)."""

@@ -1,4 +1,4 @@
-"""Test-only torch emulations of native.ce_smooth_fwd / ce_smooth_bwd (stx_ce_smooth_fwd / _bwd, csrc/st_loss.hip): the
+"""Test-only torch emulations of native.ce_smooth_fwd / ce_smooth_bwd (st_ce_smooth_fwd / _bwd, csrc/st_loss.hip): the
 closed form of the header, evaluated in the logits' own precision (fp64 logits -> an fp64 statement about the formula; the
 -m gpu tests hold the kernels to the same form).  Used inside ``tests._emul.emulated_kernels()`` for everything else."""
 import contextlib

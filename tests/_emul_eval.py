@@ -1,4 +1,4 @@
-"""Test-only torch emulations of native.ce_eval_fwd / eval_note (st3_ce_eval_fwd / st3_eval_note, csrc/st_eval.hip), in the
+"""Test-only torch emulations of native.ce_eval_fwd / eval_note (st_ce_eval_fwd / st_eval_note, csrc/st_eval.hip), in the
 conventions of tests/_emul_ce.py: the closed form of the header evaluated in the logits' own precision (fp64 logits -> an
 fp64 statement about the formula; the -m gpu tests hold the kernels to the same form on fp32 logits taken to fp64)."""
 import contextlib

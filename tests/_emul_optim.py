@@ -1,4 +1,4 @@
-"""Test-only torch emulations of the optimizer wrappers of st_amd.native's st2_ section (grad_norm_guard, adam_clip_avg,
+"""Test-only torch emulations of the optimizer wrappers of st_amd.native (grad_norm_guard, adam_clip_avg,
 swap_), like tests/_emul_ce.py: the host logic of ScheduledOptim / TrainStep runs on CPU tensors against them.  The
 arithmetic follows include/st_hip.h; it is NOT the kernels' rounding (the -m gpu tests pin that on hardware)."""
 import contextlib
@@ -24,7 +24,7 @@ def grad_norm_guard(g, scratch, out, step, guard, grad_scale=1.0):
 
 
 def averaging_weight(decay, warmup, step):
-    """w of st2_adam_clip_avg, formed in fp32 as the header spells it."""
+    """w of st_adam_clip's avg, formed in fp32 as the header spells it."""
     d = np.float32(decay)
     if warmup:
         t = np.float32(step)

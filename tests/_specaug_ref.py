@@ -1,4 +1,4 @@
-"""Test-only restatement of the SpecAugment draw (include/st_hip.h, st2_ section) in Python integers, the masks applied to
+"""Test-only restatement of the SpecAugment draw (include/st_hip.h, st_specaug_plan) in Python integers, the masks applied to
 raw and to stacked arrays with numpy, and the seeds / shapes / policies the GPU tests use - chosen HERE, on the CPU, where
 tests/test_specaug_cpu.py checks that none of them draws only empty masks.
 

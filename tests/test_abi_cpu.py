@@ -16,19 +16,13 @@ HEADER = os.path.join(ROOT, "include", "st_hip.h")
 DEV_HOOKS = {"st_dev_chain_trace"}        # development entry points: defined in csrc/, deliberately not in the header or the binding
 
 
-def _header_functions():
-    text = open(os.path.join(ROOT, "include", "st_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\bint\s+(st_[a-z0-9_]+)\s*\(", text))
+def _header_text():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
-def test_library_exports_header_symbols():
-    lib = native.load()
-    declared = _header_functions()
-    assert declared == set(native.SIGNATURES), (declared ^ set(native.SIGNATURES))
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert lib.st_version() == native.ABI_VERSION
+def _header_declarations():
+    """name -> parameter text of every `int st_*(...);` of the header, in header order."""
+    return dict(re.findall(r"\bint\s+(st_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", _header_text(), flags=re.S))
 
 
 def _source(name):
@@ -36,14 +30,32 @@ def _source(name):
         return f.read()
 
 
+def test_library_exports_header_symbols():
+    """ONE list: what the header declares == what the binding binds == what the library exports == what the sources define
+    (development hooks aside) - for every entry point, whichever feature brought it."""
+    lib = native.load()
+    declared = _header_declarations()
+    assert list(declared) == list(native.SIGNATURES), (set(declared) ^ set(native.SIGNATURES))
+    syms = subprocess.run(["nm", "-D", "--defined-only", native.lib_path()], check=True, capture_output=True, text=True).stdout
+    exported = set(re.findall(r"\bT\s+(st[a-z0-9]*_[a-z0-9_]+)$", syms, flags=re.M))
+    assert exported - DEV_HOOKS == set(declared), exported ^ set(declared)
+    for name, args in declared.items():
+        params = [] if args.strip() == "void" else args.split(",")
+        assert len(params) == len(native.SIGNATURES[name]), name
+        want = [ctypes.c_void_p if "*" in a or a.split()[0] == "st_stream_t" else native._CTYPES[" ".join(a.replace("const", " ").split()[:-1])]
+                for a in params]
+        assert want == native.SIGNATURES[name], name
+        assert isinstance(getattr(lib, name), native._Timed), name          # bound through the per-launch timing bracket
+    assert lib.st_version() == native.ABI_VERSION
+
+
 def test_sources_define_exactly_the_declared_entry_points():
-    """Every `extern "C" int st_*` of the library's sources is a declaration of the header (64 today) or a development hook -
-    and nothing the header declares is left undefined."""
+    """Every `extern "C" int st*_*` of the library's sources is a declaration of the header or a development hook - and nothing
+    the header declares is left undefined."""
     found = set()
     for src in build.SOURCES:
-        found |= set(re.findall(r'extern\s+"C"\s+int\s+(st_\w+)\s*\(', _source(src)))
-    declared = _header_functions()
-    assert len(declared) == 64
+        found |= set(re.findall(r'extern\s+"C"\s+int\s+(st[a-z0-9]*_\w+)\s*\(', _source(src)))
+    declared = set(_header_declarations())
     assert found == declared | DEV_HOOKS, (found ^ (declared | DEV_HOOKS))
 
 
@@ -75,8 +87,7 @@ def test_width_sensitive_slots_of_the_parsed_binding():
     """Pinned literally, so a parser bug cannot hide behind "derived from the header": an int where a long long belongs shifts or
     truncates the arguments of kernels that see raw pointers."""
     S = native.SIGNATURES
-    for name, args in re.findall(r"\bint\s+(st_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S),
-                                 flags=re.S):
+    for name, args in _header_declarations().items():
         n = 0 if args.strip() == "void" else args.count(",") + 1
         assert n == len(S[name]), (name, n, len(S[name]))
     assert S["st_gemm_splitk"][-1] is ctypes.c_longlong and S["st_gemm_splitk"][-2] is ctypes.c_void_p
@@ -86,7 +97,11 @@ def test_width_sensitive_slots_of_the_parsed_binding():
     assert S["st_gemm"][0] is ctypes.c_void_p and S["st_gemm"][17] is ctypes.c_void_p and len(S["st_gemm"]) == 22
     assert S["st_zero"] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong]
     assert S["st_version"] == [] and len(S["st_version"]) == 0 and S["st_wfrag_depth"] == []
-    assert S["st_adam_clip"][1] is ctypes.c_longlong and S["st_adam_clip"][-5:] == [ctypes.c_float] * 5
+    assert len(S["st_adam_clip"]) == 19 and S["st_adam_clip"][1] is ctypes.c_longlong
+    assert S["st_adam_clip"][9:14] == [ctypes.c_float] * 5          # max_norm, beta1, beta2, eps, grad_scale
+    assert S["st_adam_clip"][-5:] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
+    assert len(S["st_grad_norm"]) == 9 and S["st_grad_norm"][-2:] == [ctypes.c_void_p, ctypes.c_void_p]
+    assert S["st_grad_norm"][2] is ctypes.c_longlong and S["st_grad_norm"][6] is ctypes.c_float
     assert S["st_row_chain"][-2] is ctypes.c_longlong and S["st_row_chain"][-1] is ctypes.c_float
     assert S["st_row_chain"][22] is ctypes.c_void_p          # unsigned long long* relu_bits: a pointer, not a scalar
     assert S["st_attn_bwd"][-1] is ctypes.c_longlong and S["st_ctc_loss_fwd"][-2] is ctypes.c_longlong
@@ -108,8 +123,9 @@ def test_parser_refuses_a_type_it_does_not_know(decl, param):
 
 
 def test_version_and_epilogues_come_from_the_header():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    text = _header_text()
     assert native.ABI_VERSION == int(re.search(r"#define\s+ST_ABI_VERSION\s+(\d+)", text).group(1)) == native.load().st_version()
+    assert len(re.findall(r"#define\s+\w*VERSION\b", text)) == 1 and not [n for n in native.SIGNATURES if n.endswith("_version") and n != "st_version"]
     enum = dict(re.findall(r"\bST_(EPI_\w+)\s*=\s*(\d+)", text))
     assert len(enum) == 8 and sorted(map(int, enum.values())) == list(range(8))
     for name, value in enum.items():
@@ -117,6 +133,75 @@ def test_version_and_epilogues_come_from_the_header():
     # only the header carries the number
     assert not re.search(r"return\s+\d+\s*;", re.search(r"int st_version\(void\)[^\n]*", _source("st_misc.hip")).group(0))
     assert not re.search(r"^ABI_VERSION\s*=\s*\d", open(native.__file__).read(), flags=re.M)
+
+
+# ---- the version is a fingerprint of the declarations: derived, so no test (this one included) spells the number out -------------
+def _macro(text):
+    return int(re.search(r"#define\s+ST_ABI_VERSION\s+(\d+)", text).group(1))
+
+
+def test_the_version_is_the_fingerprint_of_the_header():
+    text = open(HEADER).read()
+    assert _macro(text) == native.abi_fingerprint(text) == native.ABI_VERSION == native.load().st_version()
+    assert native.check_fingerprint(text) == native.ABI_VERSION
+
+
+SYNTHETIC = """/* a synthetic header */
+#define ST_ABI_VERSION 0
+enum { %s };
+int st_a(st_stream_t stream, const float* p, long long n);
+int st_b(int k, float x, const void* const* X);
+int st_c(void);
+""" % ", ".join("ST_EPI_%d = %d" % (i, i) for i in range(8))
+
+
+@pytest.mark.parametrize("old,new", [
+    ("int k, float x", "long long k, float x"),                                    # a parameter's type: int -> long long
+    ("const float* p", "const float p"),                                           # ... float* -> float
+    ("long long n);", "long long n, int flag);"),                                  # a parameter added
+    ("int k, float x,", "int k,"),                                                 # ... removed
+    ("int st_c(void);", "int st_c(void);\nint st_d(int k);"),                      # a declaration added
+    ("int st_b(", "int st_bb("),                                                   # ... renamed
+    ("int st_b(int k, float x, const void* const* X);\nint st_c(void);",
+     "int st_c(void);\nint st_b(int k, float x, const void* const* X);"),          # two declarations swapped
+    ("ST_EPI_3 = 3", "ST_EPI_3 = 9"),                                              # an epilogue selector's value
+])
+def test_fingerprint_changes_with_the_abi(old, new):
+    assert SYNTHETIC.count(old) == 1
+    assert native.abi_fingerprint(SYNTHETIC.replace(old, new)) != native.abi_fingerprint(SYNTHETIC)
+
+
+@pytest.mark.parametrize("old,new", [
+    ("/* a synthetic header */", "/* another comment */"),                         # a comment edited
+    ("int k, float x", "int k, /* the count */ float x"),                          # ... added inside a parameter list
+    (", const float* p, ", ",\n         const float *p ,\n  "),                    # whitespace and line breaks
+    ("int st_c(void);", "int   st_c ( void ) ;"),
+    ("float x", "float scale"),                                                    # a parameter renamed
+    ("const float* p", "float* p"),                                                # const removed
+    ("int k", "const int k"),                                                      # ... added
+    ("const void* const* X", "void** Y"),
+])
+def test_fingerprint_ignores_what_is_not_the_abi(old, new):
+    assert SYNTHETIC.count(old) == 1
+    assert native.abi_fingerprint(SYNTHETIC.replace(old, new)) == native.abi_fingerprint(SYNTHETIC)
+
+
+def test_an_edited_declaration_fails_the_import_and_names_the_number(tmp_path):
+    """A signature edited without touching ST_ABI_VERSION: check_fingerprint, and with it `import st_amd.native` (a fresh
+    interpreter whose build.ABI_HEADER points at the edited copy), raises and prints the value to write."""
+    import sys
+    text = open(HEADER).read()
+    edited = text.replace("int st_zero(st_stream_t stream, void* ptr, long long bytes);", "int st_zero(st_stream_t stream, void* ptr, int bytes);")
+    assert edited != text
+    want = native.abi_fingerprint(edited)
+    assert want != native.ABI_VERSION
+    with pytest.raises(RuntimeError, match=r"ST_ABI_VERSION %d\b" % want):
+        native.check_fingerprint(edited)
+    assert native.check_fingerprint(re.sub(r"(#define\s+ST_ABI_VERSION\s+)\d+", r"\g<1>%d" % want, edited)) == want
+    (tmp_path / "st_hip.h").write_text(edited)
+    code = "from st_amd import build; build.ABI_HEADER = %r; import st_amd.native" % str(tmp_path / "st_hip.h")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, PYTHONPATH=os.pathsep.join(sys.path)))
+    assert r.returncode != 0 and "RuntimeError" in r.stderr and "#define ST_ABI_VERSION %d" % want in r.stderr, r.stderr[-2000:]
 
 
 def test_a_missing_header_is_a_broken_checkout(monkeypatch, tmp_path):

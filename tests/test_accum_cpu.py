@@ -1,5 +1,5 @@
 """-m "not gpu": gradient accumulation - TrainStep(accumulate=K) - on the arena path with emulated kernels (tests/_emul.py,
-tests/_emul_ce.py, tests/_emul_optim.py, tests/_emul_accum.py): the st2_ entry points of the ABI, the window's gradient against
+tests/_emul_ce.py, tests/_emul_optim.py, tests/_emul_accum.py): its entry points in the ABI, the window's gradient against
 the fp64 oracle's FULL-batch gradient, the window's bookkeeping, the guard, the untouched defaults, bucket modes and two ranks
 over gloo.  The ``run_*`` bodies take a device: tests/test_accum_gpu.py calls them on the hardware.
 
@@ -12,6 +12,7 @@ padded to: sum of B_k * l_max_k.  (LabelSmoothingLoss on the 4 utterances as ONE
 the splits below by 3 * 10 + 9 = 39 and 10 + 3 * 9 = 37: its denominator counts padding, so it is a property of how the tokens
 were batched.  The window keeps each micro-batch's own padding, as the step's docstring says.)"""
 import contextlib
+import ctypes
 import os
 import re
 import socket
@@ -33,7 +34,7 @@ from tests.test_composition_cpu import GRAD_TOL_GLOBAL, GRAD_TOL_MEDIAN, GRAD_TO
 from tests.test_label_smoothing_cpu import EPS, make_criterion
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("st2_accum_note", "st2_grad_norm_win", "st2_adam_clip_win", "st2_window_close")
+NEW = ("st_accum_note", "st_grad_norm", "st_adam_clip", "st_window_close")
 SPLITS = [[[0, 1, 2], [3]], [[0], [1, 2, 3]]]
 KINDS = ["plain", "ce", "ls"]
 
@@ -139,16 +140,16 @@ def flat_of(model, grads):
 
 
 # ---- 1. the ABI -----------------------------------------------------------------------------------------------------------------
-def test_the_four_entry_points_are_declared_bound_exported_and_defined():
-    assert set(NEW) <= set(native.EXT2_SIGNATURES)
-    lib = native.load()
-    assert lib.st2_version() == native.EXT2_VERSION == 3
-    syms = subprocess.run(["nm", "-D", "--defined-only", native.lib_path()], check=True, capture_output=True, text=True).stdout
-    assert set(NEW) <= set(re.findall(r"\bT\s+(st2_[a-z0-9_]+)", syms))
+def test_the_entry_points_are_declared_bound_and_defined():
+    """(header == binding == library == sources for EVERY entry point: tests/test_abi_cpu.py.)  The window's norm and update are
+    st_grad_norm / st_adam_clip with their last pointer: pinned by position, a window is the LAST argument of both."""
+    S = native.SIGNATURES
+    assert set(NEW) <= set(S)
     src = open(os.path.join(build.CSRC, "st_optim.hip")).read()
-    assert set(NEW) <= set(re.findall(r'extern\s+"C"\s+int\s+(st2_\w+)\s*\(', src))
-    assert len(native.EXT2_SIGNATURES["st2_adam_clip_win"]) == len(native.EXT2_SIGNATURES["st2_adam_clip_avg"]) + 1
-    assert len(native.EXT2_SIGNATURES["st2_grad_norm_win"]) == len(native.EXT2_SIGNATURES["st2_grad_norm_guard"]) + 1
+    assert set(NEW) <= set(re.findall(r'extern\s+"C"\s+int\s+(st\w+)\s*\(', src))
+    assert len(S["st_adam_clip"]) == 19 and S["st_adam_clip"][1] is ctypes.c_longlong
+    assert S["st_adam_clip"][-5:] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
+    assert len(S["st_grad_norm"]) == 9 and S["st_grad_norm"][-2:] == [ctypes.c_void_p, ctypes.c_void_p]
 
 
 def test_wrappers_check_their_arguments_before_any_launch():

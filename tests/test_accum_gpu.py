@@ -1,6 +1,6 @@
-"""-m gpu: gradient accumulation on the hardware - st2_grad_norm_win / st2_adam_clip_win against st2_grad_norm_guard /
-st2_adam_clip_avg (bit for bit at a denominator of 1) and against an fp64 evaluation of Adam per element, st2_accum_note /
-st2_window_close on exact values, then TrainStep(accumulate=K) against the fp64 oracle's full-batch gradient (the bodies of
+"""-m gpu: gradient accumulation on the hardware - st_grad_norm / st_adam_clip with a window against the forms without
+one (bit for bit at a denominator of 1) and against an fp64 evaluation of Adam per element, st_accum_note /
+st_window_close on exact values, then TrainStep(accumulate=K) against the fp64 oracle's full-batch gradient (the bodies of
 tests/test_accum_cpu.py), through bucket captures, and two consecutive windows through captured graphs.
 
 Sizes (tests/test_averaging_gpu.py): n = 4 is one 16-byte element; 1,028 one element past a workgroup; 4,194,308 one element

@@ -1,5 +1,5 @@
-"""-m gpu: the optimizer update that skips non-finite gradients and keeps averaged weights - st2_grad_norm_guard,
-st2_adam_clip_avg, st2_swap_f32 against st_grad_norm / st_adam_clip (bit for bit) and an fp64 evaluation of the averaging
+"""-m gpu: the optimizer update that skips non-finite gradients and keeps averaged weights - st_grad_norm with a guard,
+st_adam_clip with found_inf / avg, st_swap_f32 against the plain st_grad_norm / st_adam_clip (bit for bit) and an fp64 evaluation of the averaging
 recursion, then the same through TrainStep (graph mode), optimizer.averaged() and JointTrainStep(ctc="hip").
 
 Sizes: n = 4 is one 16-byte element; 1,028 one element past a 256-thread workgroup (and past a 1,024-thread one of the norm);

@@ -145,10 +145,10 @@ def test_infeasible_utterances_agree_with_the_plan():
 def test_new_exports_in_header_binding_and_library():
     names = ["st_ctc_loss_ws_kib", "st_ctc_loss_fwd", "st_ctc_loss_grad"]
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "st_hip.h")).read(), flags=re.S)
-    assert native.ABI_VERSION == 7 and re.search(r"#define\s+ST_ABI_VERSION\s+7\b", text)
+    assert native.ABI_VERSION == int(re.search(r"#define\s+ST_ABI_VERSION\s+(\d+)", text).group(1)) == native.abi_fingerprint(text)
     decl = dict(re.findall(r"\bint\s+(st_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", text, flags=re.S))
     lib = native.load()
-    assert lib.st_version() == 7
+    assert lib.st_version() == native.ABI_VERSION
     syms = subprocess.run(["nm", "-D", "--defined-only", native.lib_path()], check=True, capture_output=True, text=True).stdout
     exported = set(re.findall(r"\bT\s+(st_[a-z0-9_]+)", syms))
     for n in names:
@@ -226,8 +226,8 @@ def test_ctc_rows_hip_feeds_dlogits_what_the_truth_says(monkeypatch):
                         [1, 2, 3, 4, 5, 6, 0, 0, 0], [9, 9, 9, 0, 0, 0, 0, 0, 0]])     # utterance 1: 5 equal labels on 8 frames
     enc0 = (torch.randn(int(in_len.sum()), d) * 0.7).to(torch.bfloat16)
     log = []
-    with emulated_kernels(), emulated_ctc_loss():
-        monkeypatch.setattr(native, "ctc_dlogits", _recording_dlogits(log))
+    with emulated_kernels(), emulated_ctc_loss(), monkeypatch.context() as mp:      # (undone before the emulations are)
+        mp.setattr(native, "ctc_dlogits", _recording_dlogits(log))
         head = CTCAttentionLoss(d, V, ctc_weight=0.3)
         plan = head.plan(tgt, tgt_len, in_len, F_.Rows.packed(in_len, "cpu"))
         head.zero_grad_buffers()
@@ -272,8 +272,8 @@ def test_joint_trainstep_hip_eager_feeds_dlogits_what_the_truth_says(monkeypatch
     monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: pytest.fail("the HIP path must not touch streams"))
     for impl in ("hip",):
         log = []
-        with emulated_kernels(), emulated_ctc_loss():
-            monkeypatch.setattr(native, "ctc_dlogits", _recording_dlogits(log))
+        with emulated_kernels(), emulated_ctc_loss(), monkeypatch.context() as mp:      # (undone before the emulations are)
+            mp.setattr(native, "ctc_dlogits", _recording_dlogits(log))
             torch.manual_seed(0)
             model = M.Transformer(cfg).eval()
             U.init_parameters(model)

@@ -1,5 +1,5 @@
-"""-m "not gpu": forward-only validation (st_amd/evaluate.py:EvalStep over st3_ce_eval_fwd / st3_eval_note, csrc/st_eval.hip) -
-the st3_ section of the ABI, the wrappers' argument checks, the closed form of the two kernels (tests/_emul_eval.py) against
+"""-m "not gpu": forward-only validation (st_amd/evaluate.py:EvalStep over st_ce_eval_fwd / st_eval_note, csrc/st_eval.hip) -
+its entry points in the ABI, the wrappers' argument checks, the closed form of the two kernels (tests/_emul_eval.py) against
 torch in fp64 on the committed loss fixture, the constructor's refusals, and the driver itself on the emulated kernels.
 The ``run_*`` bodies take a device: tests/test_eval_gpu.py calls them on the hardware."""
 import contextlib
@@ -38,41 +38,23 @@ def emulated():
         yield
 
 
-# ---- 1. the third extension section of the ABI ----------------------------------------------------------------------------
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return text, dict(re.findall(r"\bint\s+(st3_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", text, flags=re.S))
-
-
-def test_st3_section_is_declared_bound_exported_and_defined():
-    text, decl = _declared()
-    assert {"st3_version", "st3_ce_eval_fwd", "st3_eval_note"} <= set(decl)
-    assert set(decl) == set(native.EXT3_SIGNATURES)
-    for name, args in decl.items():
-        assert (0 if args.strip() == "void" else args.count(",") + 1) == len(native.EXT3_SIGNATURES[name]), name
-    others = set(native.SIGNATURES) | set(native.EXT_SIGNATURES) | set(native.EXT2_SIGNATURES)
-    assert not set(decl) & others
-    syms = subprocess.run(["nm", "-D", "--defined-only", native.lib_path()], check=True, capture_output=True, text=True).stdout
-    assert set(re.findall(r"\bT\s+(st3_[a-z0-9_]+)", syms)) == set(decl)
+# ---- 1. the two entry points in the ABI (header == binding == library == sources: tests/test_abi_cpu.py, for every entry point) ---
+def test_eval_entry_points_are_declared_bound_and_defined():
+    assert {"st_ce_eval_fwd", "st_eval_note"} <= set(native.SIGNATURES)
     assert "st_eval.hip" in build.SOURCES
     src = open(os.path.join(build.CSRC, "st_eval.hip")).read()
-    assert set(re.findall(r'extern\s+"C"\s+int\s+(st3_\w+)\s*\(', src)) == set(decl)
-    # no other source defines into the section
+    assert set(re.findall(r'extern\s+"C"\s+int\s+(st\w+)\s*\(', src)) == {"st_ce_eval_fwd", "st_eval_note"}
+    # no other source defines them
     for other in build.SOURCES:
         if other != "st_eval.hip":
-            assert not re.findall(r'extern\s+"C"\s+int\s+(st3_\w+)\s*\(', open(os.path.join(build.CSRC, other)).read()), other
-    lib = native.load()
-    for name in decl:
-        assert isinstance(getattr(lib, name), native._Timed), name
+            assert not re.findall(r'extern\s+"C"\s+int\s+(st_ce_eval_fwd|st_eval_note)\s*\(', open(os.path.join(build.CSRC, other)).read()), other
 
 
 def test_versions():
-    text, _ = _declared()
-    lib = native.load()
-    assert lib.st3_version() == native.EXT3_VERSION == int(re.search(r"#define\s+ST3_VERSION\s+(\d+)", text).group(1)) == 1
-    # the other three are where their own tests pin them
-    assert (native.ABI_VERSION, native.EXT_VERSION, native.EXT2_VERSION) == (7, 1, 3)
-    assert (lib.st_version(), lib.stx_version(), lib.st2_version()) == (7, 1, 3)
+    """One version, and it is the header's fingerprint - whatever its value (tests/test_abi_cpu.py holds the fingerprint itself)."""
+    text = open(HEADER).read()
+    assert native.load().st_version() == native.ABI_VERSION == native.abi_fingerprint(text)
+    assert not [n for n in native.SIGNATURES if n.endswith("_version") and n != "st_version"]
 
 
 # ---- 2. the wrappers refuse before any launch --------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""-m gpu: forward-only validation on the hardware - st3_ce_eval_fwd / st3_eval_note (csrc/st_eval.hip) against the fp64 closed
+"""-m gpu: forward-only validation on the hardware - st_ce_eval_fwd / st_eval_note (csrc/st_eval.hip) against the fp64 closed
 form of tests/_emul_eval.py on the same fp32 logits, then st_amd/evaluate.py:EvalStep: consistency with the logits
 forward_packed returns, the fp64 oracle, bucket graphs against eager launches bit for bit, training left alone, averaged weights.
 
@@ -8,7 +8,7 @@ relative on the batch's sum (its loss check).  Hits, token counts and states are
 
 Shapes: V crosses every boundary of the row reduction - 1 column, fewer than a wave (7, 63), exactly one / one more (64, 65), fewer
 than / exactly / one more than the workgroup's 256-column stride (255, 256, 257), exactly / one more than one 2,048-column chunk
-of the loop (2048, 2049), the flagship vocabulary (4233); R = 1, 3 and 300 rows (more rows than st3_eval_note has threads)."""
+of the loop (2048, 2049), the flagship vocabulary (4233); R = 1, 3 and 300 rows (more rows than st_eval_note has threads)."""
 import functools
 
 import pytest

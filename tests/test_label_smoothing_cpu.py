@@ -1,6 +1,6 @@
 """-m "not gpu": label-smoothed cross-entropy on the HIP loss path - the closed form the kernels implement (held to three fp64
-references through the test-only emulation tests/_emul_ce.py), the criterion -> kernel mapping (functional.ce_spec), the stx_*
-extension section of the ABI, and the wiring through TrainStep(criterion=...) / JointTrainStep against the fp64 oracle.
+references through the test-only emulation tests/_emul_ce.py), the criterion -> kernel mapping (functional.ce_spec), the two
+entry points in the ABI, and the wiring through TrainStep(criterion=...) / JointTrainStep against the fp64 oracle.
 
 The ``run_*`` bodies take a device: tests/test_label_smoothing_gpu.py calls the same bodies on the hardware."""
 import copy
@@ -100,38 +100,17 @@ def test_ce_spec_table():
             F_.ce_spec(crit, V)
 
 
-# ---- 3. the extension section of the ABI -----------------------------------------------------------------------------------
-def test_extension_section_of_the_abi():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "st_hip.h")).read(), flags=re.S)
-    decl = dict(re.findall(r"\bint\s+(stx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", text, flags=re.S))
-    assert set(decl) == set(native.EXT_SIGNATURES) == {"stx_version", "stx_ce_smooth_fwd", "stx_ce_smooth_bwd"}
-    assert not set(native.EXT_SIGNATURES) & set(native.SIGNATURES)
-    for name, args in decl.items():
-        n = 0 if args.strip() == "void" else args.count(",") + 1
-        assert n == len(native.EXT_SIGNATURES[name]), name
-    assert native.EXT_VERSION == int(re.search(r"#define\s+STX_VERSION\s+(\d+)", text).group(1)) == 1
-    lib = native.load()
-    assert lib.stx_version() == native.EXT_VERSION
-    syms = subprocess.run(["nm", "-D", "--defined-only", native.lib_path()], check=True, capture_output=True, text=True).stdout
-    exported = set(re.findall(r"\bT\s+(stx_[a-z0-9_]+)", syms))
-    assert exported == set(decl), exported ^ set(decl)
-    for name in decl:
-        assert isinstance(getattr(lib, name), native._Timed), name          # bound through the per-launch timing bracket
-    fwd, bwd = native.EXT_SIGNATURES["stx_ce_smooth_fwd"], native.EXT_SIGNATURES["stx_ce_smooth_bwd"]
+# ---- 3. the two entry points in the ABI (header == binding == library == sources: tests/test_abi_cpu.py, for every entry point) ---
+def test_smoothed_entry_points_of_the_abi():
+    assert {"st_ce_smooth_fwd", "st_ce_smooth_bwd"} <= set(native.SIGNATURES)
+    fwd, bwd = native.SIGNATURES["st_ce_smooth_fwd"], native.SIGNATURES["st_ce_smooth_bwd"]
     assert fwd[8] is ctypes.c_float and fwd[9] is ctypes.c_float and fwd[10] is ctypes.c_int and fwd[11] is ctypes.c_void_p
     assert bwd[8] is ctypes.c_float and bwd[9] is ctypes.c_float and bwd[10] is ctypes.c_int and bwd[11] is ctypes.c_void_p
     assert fwd[0] is ctypes.c_void_p and fwd[7] is ctypes.c_int and len(fwd) == 15 and len(bwd) == 17 and bwd[-1] is ctypes.c_int
     assert "st_loss.hip" in build.SOURCES
     src = open(os.path.join(build.CSRC, "st_loss.hip")).read()
     assert re.search(r'^\s*#\s*include\s+"st_hip.h"', src, flags=re.M)
-    found = set(re.findall(r'extern\s+"C"\s+int\s+(stx_\w+)\s*\(', src))
-    assert found == set(decl)
-    # the extension parser obeys the same parameter rules, and the base parser does not see the section
-    with pytest.raises(RuntimeError, match="double x"):
-        native.parse_extension("#define STX_VERSION 1\nint stx_a(st_stream_t stream, double x);\n")
-    sigs, ver = native.parse_extension("#define STX_VERSION 7\nint stx_a(const float* p, long long n);\nint st_b(int k);\n")
-    assert sigs == {"stx_a": [ctypes.c_void_p, ctypes.c_longlong]} and ver == 7
-    assert not any(n.startswith("stx_") for n in native.parse_header(open(os.path.join(ROOT, "include", "st_hip.h")).read())[0])
+    assert set(re.findall(r'extern\s+"C"\s+int\s+(st\w+)\s*\(', src)) == {"st_ce_smooth_fwd", "st_ce_smooth_bwd"}
 
 
 def test_binding_argument_checks_raise_before_any_launch():

@@ -1,4 +1,4 @@
-"""-m gpu: the label-smoothed cross-entropy kernels (stx_ce_smooth_fwd / stx_ce_smooth_bwd, csrc/st_loss.hip + st_ce.cuh) against
+"""-m gpu: the label-smoothed cross-entropy kernels (st_ce_smooth_fwd / st_ce_smooth_bwd, csrc/st_loss.hip + st_ce.cuh) against
 the fp64 closed form, their plain instantiation against st_ce_fwd / st_ce_bwd bit for bit, and the bodies of
 tests/test_label_smoothing_cpu.py on the hardware: TrainStep(criterion=...) eager / captured / in both bucket modes, and the
 joint CTC + attention step as one graph."""
@@ -93,7 +93,7 @@ def test_smoothed_kernels_match_the_fp64_closed_form(R, V):
 
 @pytest.mark.parametrize("R,V", [(7, 30), (37, 2049), (9, 4337)])
 def test_plain_instantiation_is_the_same_body(R, V):
-    """stx_ce_smooth_* at (1, 0, -1, NULL) with V = v_pad == st_ce_fwd / st_ce_bwd, bit for bit: one kernel body, one reduction
+    """st_ce_smooth_* at (1, 0, -1, NULL) with V = v_pad == st_ce_fwd / st_ce_bwd, bit for bit: one kernel body, one reduction
     order."""
     logits, target, vp, _ = _case(R, V)
     lg, tg = logits.cuda()[:, :vp], target.cuda()          # (a column slice: ldl = v_pad + 8)

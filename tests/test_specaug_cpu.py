@@ -1,4 +1,4 @@
-"""-m "not gpu": SpecAugment's host side - the policy object's argument checks, the st2_ section of the C ABI, the wrappers'
+"""-m "not gpu": SpecAugment's host side - the policy object's argument checks, its entry points in the C ABI, the wrappers'
 checks, the Python restatement of the draw (tests/_specaug_ref.py) and the seeds the GPU tests (tests/test_specaug_gpu.py)
 run with.  No kernel is launched here."""
 import ctypes
@@ -50,46 +50,12 @@ def test_encoder_attribute_is_plain():
     assert set(enc.state_dict()) == keys and not any("spec" in k for k in keys)
 
 
-# ---- 2. the st2_ section of the ABI: header, binding, library and sources agree - nothing spelled out here ---------------------
-def test_second_extension_section_of_the_abi():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "st_hip.h")).read(), flags=re.S)
-    decl = dict(re.findall(r"\bint\s+(st2_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", text, flags=re.S))
-    assert len(decl) >= 2 and "st2_version" in decl                      # (the version query and at least one entry point)
-    assert set(decl) == set(native.EXT2_SIGNATURES)
-    assert not set(decl) & (set(native.SIGNATURES) | set(native.EXT_SIGNATURES))
-    for name, args in decl.items():
-        n = 0 if args.strip() == "void" else args.count(",") + 1
-        assert n == len(native.EXT2_SIGNATURES[name]), name
-        want = [ctypes.c_void_p if "*" in a or a.split()[0] == "st_stream_t" else native._CTYPES[" ".join(a.replace("const", " ").split()[:-1])]
-                for a in ([] if args.strip() == "void" else args.split(","))]
-        assert want == native.EXT2_SIGNATURES[name], name
-    assert native.EXT2_VERSION == int(re.search(r"#define\s+ST2_VERSION\s+(\d+)", text).group(1))
-    lib = native.load()
-    assert lib.st2_version() == native.EXT2_VERSION
-    syms = subprocess.run(["nm", "-D", "--defined-only", native.lib_path()], check=True, capture_output=True, text=True).stdout
-    exported = set(re.findall(r"\bT\s+(st2_[a-z0-9_]+)", syms))
-    assert exported == set(decl), exported ^ set(decl)
-    for name in decl:
-        assert isinstance(getattr(lib, name), native._Timed), name          # bound through the per-launch timing bracket
-    found = set()
-    for src in build.SOURCES:
-        found |= set(re.findall(r'extern\s+"C"\s+int\s+(st2_\w+)\s*\(', open(os.path.join(build.CSRC, src)).read()))
-    assert found == set(decl), found ^ set(decl)
+# ---- 2. the entry points in the ABI (header == binding == library == sources: tests/test_abi_cpu.py, for every entry point) -------
+def test_specaug_entry_points_of_the_abi():
+    assert {"st_specaug_plan", "st_pack_rows_aug", "st_feat_stack_aug"} <= set(native.SIGNATURES)
     assert "st_augment.hip" in build.SOURCES
-    # only the header carries the number
-    assert not re.search(r"^EXT2_VERSION\s*=\s*\d", open(native.__file__).read(), flags=re.M)
-
-
-def test_parse_extension_takes_a_prefix():
-    text = "#define STX_VERSION 7\n#define ST2_VERSION 3\nint stx_a(const float* p, long long n);\nint st2_b(int k, unsigned s);\nint st_c(int k);\n"
-    assert native.parse_extension(text) == ({"stx_a": [ctypes.c_void_p, ctypes.c_longlong]}, 7)            # the default: as before
-    assert native.parse_extension(text, "st2") == ({"st2_b": [ctypes.c_int, ctypes.c_uint]}, 3)
-    with pytest.raises(RuntimeError, match="double x"):
-        native.parse_extension("#define ST2_VERSION 1\nint st2_a(st_stream_t stream, double x);\n", "st2")
-    with pytest.raises(RuntimeError, match="st9_"):
-        native.parse_extension(text, "st9")
-    header = open(os.path.join(ROOT, "include", "st_hip.h")).read()
-    assert not any(n.startswith("st2_") for n in list(native.parse_header(header)[0]) + list(native.parse_extension(header)[0]))
+    src = open(os.path.join(build.CSRC, "st_augment.hip")).read()
+    assert set(re.findall(r'extern\s+"C"\s+int\s+(st\w+)\s*\(', src)) == {"st_specaug_plan", "st_pack_rows_aug", "st_feat_stack_aug"}
 
 
 # ---- 3. the wrappers raise before any launch -------------------------------------------------------------------------------------

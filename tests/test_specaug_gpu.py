@@ -71,7 +71,7 @@ def test_plan_matches_the_restatement(i):
 @pytest.mark.parametrize("ci", range(len(ref.STACK_TRIPLES)))
 @pytest.mark.parametrize("with_stats", [False, True])
 def test_feat_stack_aug_equals_feat_stack_of_masked_input(ci, with_stats):
-    """st2_feat_stack_aug(x) == st_feat_stack(host-masked x), into a strided guarded view.  Host-masked: a masked element is 0
+    """st_feat_stack_aug(x) == st_feat_stack(host-masked x), into a strided guarded view.  Host-masked: a masked element is 0
     - with CMVN statistics it is the fp32 mean st_feat_stack itself computes (sum / count: one correctly rounded division on
     either side), which CMVN maps to exactly +0.0, the value the mask stands for (the mean after CMVN)."""
     from st_amd.features import stack_frames

@@ -3,8 +3,8 @@
 32 utterances of 500..1000 frames, graph mode) - same box, same process, ALTERNATELY: --repeats rounds of --windows timed windows
 each of
   plain   K non-accumulating steps (TrainStep as it always was: zero_grad, forward, backward, norm, clip + Adam - K times),
-  accum   K micro-batches + ONE update (TrainStep(accumulate=K): no zero_grad launch, st2_accum_note per micro-batch;
-          st2_grad_norm_win, st2_adam_clip_win, st2_window_close once).
+  accum   K micro-batches + ONE update (TrainStep(accumulate=K): no zero_grad launch, st_accum_note per micro-batch;
+          st_grad_norm, st_adam_clip with the window, st_window_close once).
 Both share the model; each has its own optimizer and its own captured graphs.  As in bench.py the update runs at a learning
 rate of zero, so every timed step computes from the same weights.  Prints one JSON line and writes it to --out: ms per window of
 every round, the medians, the spread of the repeats and accum minus plain.

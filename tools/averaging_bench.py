@@ -3,7 +3,7 @@
 32 utterances of 500..1000 frames, graph mode) - same box, same process, ALTERNATELY: --repeats rounds of --steps timed steps
 each of
   plain       ScheduledOptim as it always was (st_grad_norm, st_adam_clip),
-  guard       enable_nonfinite_guard() (st2_grad_norm_guard, st2_adam_clip_avg with found_inf),
+  guard       enable_nonfinite_guard() (st_grad_norm with a guard, st_adam_clip with found_inf),
   guard_avg   guard + enable_averaging() (the same two launches; the update also reads and writes the averaged copy).
 The three steps share the model; each has its own optimizer (the options are per optimizer) and its own captured graph.  As in
 bench.py the update runs at a learning rate of zero, so every timed step computes from the same weights - the kernels move the

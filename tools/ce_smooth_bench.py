@@ -2,7 +2,7 @@
 """The label-smoothed cross-entropy against the plain one, same box, same process, ALTERNATELY.
 
 (1) Kernels at BASELINE config 2's decoder shape (the seed-0 batch's target rows x V 4337, logits [R, v_pad] fp32 with the
-    padding columns at -1e30): ``st_ce_fwd + st_ce_bwd`` against ``stx_ce_smooth_fwd + stx_ce_smooth_bwd`` (the reference's
+    padding columns at -1e30): ``st_ce_fwd + st_ce_bwd`` against ``st_ce_smooth_fwd + st_ce_smooth_bwd`` (the reference's
     LabelSmoothingLoss spec, with its denominator), device events around each pair, --repeats rounds of --iters pairs each.
     Both move the same bytes (forward reads R x V x 4; backward reads that again and writes R x v_pad x 2), so the expectation
     is a ratio inside the spread of the rounds.
@@ -76,7 +76,7 @@ def main():
         nv.ce_smooth_fwd(lg, tg, 0, spec.confidence, spec.smooth, spec.zero_col, lse, sums4, V=V, denom=denom)
         nv.ce_smooth_bwd(lg, tg, 0, spec.confidence, spec.smooth, spec.zero_col, lse, sums4, go, dl, V=V, denom=denom)
 
-    pairs = {"st_ce": plain, "stx_ce_smooth": smooth}
+    pairs = {"st_ce": plain, "st_ce_smooth": smooth}
     for fn in pairs.values():
         for _ in range(20):
             fn()
@@ -94,7 +94,7 @@ def main():
     out = {"shape": "config 2 decoder: R %d rows, V %d (v_pad %d), fp32 logits, bf16 gradient" % (R, V, vp),
            "device": torch.cuda.get_device_name(), "iters_per_round": args.iters,
            "kernels_us_per_fwd_bwd_pair": {k: _stats(v) for k, v in rounds.items()}}
-    a, b = out["kernels_us_per_fwd_bwd_pair"]["st_ce"], out["kernels_us_per_fwd_bwd_pair"]["stx_ce_smooth"]
+    a, b = out["kernels_us_per_fwd_bwd_pair"]["st_ce"], out["kernels_us_per_fwd_bwd_pair"]["st_ce_smooth"]
     out["smooth_over_plain_ratio"] = round(b["median"] / a["median"], 4)
     out["spread_over_median"] = round(max(a["spread"] / a["median"], b["spread"] / b["median"]), 4)
     out["ratio_inside_the_spread"] = bool(abs(out["smooth_over_plain_ratio"] - 1.0) <= out["spread_over_median"])

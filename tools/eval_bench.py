@@ -2,7 +2,7 @@
 """What a validation batch costs (BASELINE config 2: 6+6 layers, d_model 256, V 4337, the seed-0 batch of 32 utterances of
 500..1000 frames - the bench.py batch - in eval mode), and that the training step did not move.  One process times, ALTERNATELY
 over --repeats rounds of --batches timed calls each, the variants asked for with --only (default: all):
-  eval_eager  EvalStep(use_graph=False): forward_packed + st3_ce_eval_fwd + st3_eval_note, launched from the host
+  eval_eager  EvalStep(use_graph=False): forward_packed + st_ce_eval_fwd + st_eval_note, launched from the host
   eval_graph  EvalStep(use_graph=True, bucket=(1000, 50)): the same as one replayed bucket graph over the PADDED layouts
               (32 x 1000 frame rows where the batch has 24,060)
   eval_graph_packed  ... with bucket_rows=(24576, 1440), the packed capacities bench.py gives TrainStep for this loader
