@@ -152,7 +152,19 @@ int st_wgrad_wide(st_stream_t stream, int n, const void* const* X, const int* ld
  * (Models.py:28-33,42-44).  Saves xhat (bf16 [M,N]) and rstd (f32 [M]) for the
  * backward; `pre` (optional) receives the pre-LN value (front-end ReLU mask).
  * drop_where: 1 = dropout on act(X W^T + bias) before the LayerNorm
- * (Models.py:31), 2 = dropout on the LayerNorm output (SubLayers.py:27). */
+ * (Models.py:31), 2 = dropout on the LayerNorm output (SubLayers.py:27).
+ *
+ * The statistic (the contract of every LayerNorm in this library: here, st_row_chain, st_row_chain512, the PRE stage of
+ * st_attn_f1_fwd and - the same code, not measured on its own - of st_attn_sf1_fwd): v = act(X W^T + bias) + res in fp32; mean = sum v / N; var = sum (v - mean)^2 / N - the
+ * BIASED variance over the N columns; rstd = (var + eps)^-1/2 with eps INSIDE the root; xhat = (v - mean) rstd; rstd, xhat
+ * and out come from the same mean and variance.  Accuracy: rstd within 1e-4 (relative, every row) of the same quantities
+ * computed in fp64 from the operands as given - for rows whose mean lies up to 512 row standard deviations from zero (through
+ * the bias or the residual), for rows whose variance is comparable to eps or far below it, and for a constant row, whose xhat is
+ * +-0 in every element, whose out is bf16(beta) and whose rstd is eps^-1/2.  (This kernel and the 32-row chain kernels take
+ * the mean first and the squared deviations then; the pipelined chain kernels sum once, about a per-row pivot - see
+ * st_row_chain.  tests/test_ln_stats_gpu.py holds to it: every kernel variant st_gemm_ln dispatches to without dropout, the
+ * 32-row, split and pipelined 64- / 96-row kernels of st_row_chain, st_row_chain512 and st_attn_f1_fwd; measured:
+ * profiles/ln_stats_accuracy.txt.) */
 int st_gemm_ln(st_stream_t stream, const void* X, int ldx, const void* W, int M, int N, int K, const float* bias,
                const void* res, int ldres, const float* gamma, const float* beta, float eps, int relu,
                const float* pe, const int* pos, void* out, int ldo, void* xhat, float* rstd, void* pre,
@@ -194,7 +206,14 @@ int st_gemm_lnbwd(st_stream_t stream, const void* dY, int lddy, const void* W, i
  * block: each does PRE, ONE 256-wide chunk of the hidden dimension and leaves its partial of the second GEMM in the
  * scratch; the last of a row block's workgroups adds them (in chunk order: the result does not depend on arrival order, but
  * differs in rounding from the one-workgroup chain) and finishes the chain.  Launches that share the scratch must be
- * ordered on one stream. */
+ * ordered on one stream.
+ * Both LayerNorms keep st_gemm_ln's contract of the statistic (biased variance over the 256 columns, eps inside the root, rstd
+ * within 1e-4 of fp64 on off-centre, tiny-spread and constant rows) at every M.  Past 8,192 rows the pipelined kernels
+ * (csrc/st_rowchain_pipe.cuh) form it from ONE pass: the fp32 sum and sum of squares of v - pivot, pivot = the row's residual
+ * at column 0 plus the bias there.  Its domain: the loss of such a pass is 2^-24 rho^2 of rstd, rho = |mean of (v - pivot)| /
+ * row std - of order one as long as column 0 of the row lies within a few standard deviations of the row's mean, whatever that
+ * mean is.  (About zero instead of the pivot - the form before - the same law put rstd off by 1.5e-4 at a row mean of 32
+ * standard deviations and 4.6e-2 at 512: profiles/ln_stats_accuracy_before.txt.) */
 int st_wfrag_depth(void);
 int st_wfrag_build(st_stream_t stream, const long long* table, int n_blocks);
 int st_row_chain(st_stream_t stream, int M, const void* wfrag, int n_blocks, int next_blocks, float eps, const void* A,
@@ -216,7 +235,9 @@ int st_row_chain(st_stream_t stream, int M, const void* wfrag, int n_blocks, int
  *   projection: (u, j = 0, 1)          (h: output-column half, j: input-column half of the 512-wide matrices)
  * - st_amd.chains.encoder512_blocks spells it.  PRE and FFN are both required; post_blocks is 0 or 6 (a q | k | v projection
  * to 1,536 columns, key columns 512 .. 1023 scaled by post_kscale as st_row_chain does).  64-row workgroups; relu_bits:
- * st_row_chain512_mask_words(M, d_ff) words.  n_blocks = 4 + 4 d_ff / 256 + 2 post_blocks. */
+ * st_row_chain512_mask_words(M, d_ff) words.  n_blocks = 4 + 4 d_ff / 256 + 2 post_blocks.
+ * The statistic of both LayerNorms: st_gemm_ln's contract over the 512 columns, from one pass about the per-row pivot at every M
+ * (as st_row_chain's pipelined kernels: same domain, same accuracy). */
 int st_row_chain512(st_stream_t stream, int M, const void* wfrag, int n_blocks, int next_blocks, float eps, const void* A, int lda,
                     const void* R, int ldr, const float* bo, const float* g0, const float* be0, void* out0, void* xhat0,
                     float* rstd0, int d_ff, const float* b1, const float* b2, const float* g1, const float* be1, void* H,

@@ -17,9 +17,10 @@
 //     c - 1 hides under W1_(c+1).  The streams stay in chunk order (the 32-row kernels read them front to back): this kernel
 //     addresses blocks by position;
 //   * the bias enters through the accumulator's initial value (requested one block ahead), the ReLU mask bits are the sign
-//     bits of the fp32 sums gathered with one v_alignbit each, LayerNorm's mean and variance come from ONE pass (sum and sum
-//     of squares; fp32, 256 values of order one) and one exchange, the residual tile of the first LayerNorm is stored to LDS
-//     behind the first block (it arrives under its MFMAs);
+//     bits of the fp32 sums gathered with one v_alignbit each, LayerNorm's mean and variance come from ONE pass and one
+//     exchange: the sum and the sum of squares, in fp32, of the row's DISTANCES FROM A PIVOT - the row's residual at column 0
+//     plus the bias there, a value inside or next to the row's range (see epi_ln_p for what the plain sums lose off centre);
+//     the residual tile of the first LayerNorm is stored to LDS behind the first block (it arrives under its MFMAs);
 //   * tile copies leave through buffer descriptors whose range ends at the workgroup's last valid row: no per-piece
 //     predicate, no branch inside a block.
 #pragma once
@@ -51,13 +52,28 @@ template <int MT> __device__ __forceinline__ void bias_load(const Ctx<MT>& c, co
 #pragma unroll
   for (int g = 0; g < 4; ++g) r.v[g] = *reinterpret_cast<const f32x4*>(b + c.wave * 32 + 8 * g + 4 * c.hi);
 }
-template <int MT> __device__ __forceinline__ void acc_init(f32x16 (&acc)[MT], const BiasRegs& r) {
+// (pb: subtracted from the bias - the accumulators in front of a LayerNorm start at bias - bias[0], see epi_ln_p)
+template <int MT> __device__ __forceinline__ void acc_init(f32x16 (&acc)[MT], const BiasRegs& r, float pb = 0.f) {
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[mt][4 * g + e] = r.v[g][e];
+      for (int e = 0; e < 4; ++e) acc[mt][4 * g + e] = r.v[g][e] - pb;
+}
+// ... at bias - the row's whole pivot, bias[0] + res[row][0], where the residual tile is complete in LDS when the accumulators
+// are set up: the epilogue then subtracts nothing (st_row_chain512's second LayerNorm, whose residual is the chain's running
+// activation - there the subtraction in the epilogue showed in the step time, here it stayed inside the run-to-run spread)
+template <int MT> __device__ __forceinline__ void acc_init_pivot(const Ctx<MT>& c, f32x16 (&acc)[MT], const BiasRegs& r, float pb,
+                                                                 const bf16* res, int pitch) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const float pv = pb + (float)res[(mt * 32 + c.r) * pitch];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[mt][4 * g + e] = r.v[g][e] - pv;
+  }
 }
 
 // ---- a finished LDS tile on its way to HBM: piece p = rows (tid >> 5) + 16 p, 16 bytes at column (tid & 31) * 8
@@ -307,6 +323,15 @@ __device__ __forceinline__ void block_mma_p(Ctx<MT>& c, const bf16x8* cur_blk, c
 // exchange; xhat -> t_xhat, (dropped) output -> t_out (may be `res` itself: every residual read precedes the barrier).  One
 // workgroup barrier inside; the caller places the one behind.  red2: [MT][32 rows][8 waves x (sum, sq) + pad] floats, row
 // pitch 80 bytes (conflict-free 16-byte reads).
+//
+// The sums run over d = v - pivot, pivot = bias[0] + res[row][0] - a value inside or next to the row's range: the accumulators
+// arrive holding acc - bias[0] (acc_init subtracts it from the bias they start from, so the GEMM is summed at the size of the row's
+// spread, not of its mean) and the residual enters as res - res[row][0].  Mean, variance (biased, over all 256 columns), rstd, xhat
+// and the output all come from these d: var = sum d^2 / N - (sum d / N)^2 loses 2^-24 rho^2 of its value, rho = |mean of d| / std -
+// of order one with this pivot, whatever the row's own mean is (profiles/ln_stats_accuracy.txt: rstd against fp64 up to a row mean
+// 512 standard deviations off).  The plain sums (pivot 0) lost 1.5e-4 of rstd at a row mean of 32 standard deviations, 2.3e-3 at
+// 128, 4.6e-2 at 512 (profiles/ln_stats_accuracy_before.txt).  A constant row has d = 0 in every column: xhat = 0 and
+// rstd = eps^-1/2 exactly.
 constexpr int RED2_PITCH = 20;
 // x + the value of the lane 32 away: one v_permlane32_swap (VALU) instead of the ds_bpermute __shfl_xor becomes (an LDS round trip)
 __device__ __forceinline__ float wave_sum32(float x) {
@@ -325,6 +350,9 @@ __device__ __forceinline__ void epi_ln_p(const Ctx<MT>& c, f32x16 (&acc)[MT], co
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int g = 0; g < 4; ++g) rr[mt][g] = *reinterpret_cast<const bf16x4*>(res + (mt * 32 + c.r) * AS + j0 + 8 * g + 4 * c.hi);
+  float pv[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) pv[mt] = (float)res[(mt * 32 + c.r) * AS];
   float s[MT], q[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
@@ -333,7 +361,7 @@ __device__ __forceinline__ void epi_ln_p(const Ctx<MT>& c, f32x16 (&acc)[MT], co
     for (int g = 0; g < 4; ++g)
 #pragma unroll
       for (int e = 0; e < 4; e += 2) {
-        const float v0 = acc[mt][4 * g + e] + (float)rr[mt][g][e], v1 = acc[mt][4 * g + e + 1] + (float)rr[mt][g][e + 1];
+        const float v0 = acc[mt][4 * g + e] + ((float)rr[mt][g][e] - pv[mt]), v1 = acc[mt][4 * g + e + 1] + ((float)rr[mt][g][e + 1] - pv[mt]);
         acc[mt][4 * g + e] = v0;
         acc[mt][4 * g + e + 1] = v1;
         s0 += v0; s1 += v1;
@@ -361,7 +389,7 @@ __device__ __forceinline__ void epi_ln_p(const Ctx<MT>& c, f32x16 (&acc)[MT], co
   for (int mt = 0; mt < MT; ++mt) {
     const float ss = (pp[mt][0][0] + pp[mt][0][2]) + (pp[mt][1][0] + pp[mt][1][2]) + ((pp[mt][2][0] + pp[mt][2][2]) + (pp[mt][3][0] + pp[mt][3][2]));
     const float qq = (pp[mt][0][1] + pp[mt][0][3]) + (pp[mt][1][1] + pp[mt][1][3]) + ((pp[mt][2][1] + pp[mt][2][3]) + (pp[mt][3][1] + pp[mt][3][3]));
-    const float mean = ss * (1.f / DM);
+    const float mean = ss * (1.f / DM);      // (of d: the row's mean is pivot + mean)
     const float var = fmaxf(qq * (1.f / DM) - mean * mean, 0.f);
     rstd[mt] = rsqrtf(var + eps);
     nm[mt] = -mean * rstd[mt];
@@ -432,12 +460,14 @@ __global__ __launch_bounds__(512, 1) void row_chain_pipe_kernel(ChainArgs a) {
   TileOut pend[3];       // copies waiting for a block to hide under
   int npend = 0;
   BiasRegs nb1, nb2;     // biases on request one block ahead of the accumulator they initialise
+  float pb2 = 0.f;       // b2[0]: the bias part of the second LayerNorm's pivot (epi_ln_p)
 
   if (PRE) {
     TileRegs<MT> ra, rr;
     BiasRegs bo, g0, be0;
     tile_load(c, a.A, a.lda, ra);
     bias_load(c, a.bo, bo);
+    const float pb0 = a.bo[0];         // the bias part of the LayerNorm's pivot (epi_ln_p): asked for with the vector
 #if ST_PIPE_R_LATE
     // the residual is asked for only once A is here: both tiles on request together share the HBM burst of the launch's first
     // microseconds (every CU asks at once), and the first block needs A alone
@@ -453,7 +483,7 @@ __global__ __launch_bounds__(512, 1) void row_chain_pipe_kernel(ChainArgs a) {
     __syncthreads();
     TRP(1);
     f32x16 acc[MT];
-    acc_init(acc, bo);
+    acc_init(acc, bo, pb0);
     NoSide ns;
     block_mma_p(c, blk(0), blk(1), T0, acc, ns);
     TRP(2);
@@ -461,6 +491,7 @@ __global__ __launch_bounds__(512, 1) void row_chain_pipe_kernel(ChainArgs a) {
     if (FFN) {                         // (requested here, used behind the LayerNorm: a bias asked for where it is needed drains the
       bias_load(c, a.b2, nb2);         // whole in-order queue - ring, copies - in front of the block: 0.65 us per block, measured)
       bias_load(c, a.b1, nb1);
+      pb2 = a.b2[0];
     }
     __syncthreads();                   // residual visible; every wave is past its MFMAs on the A tile
     epi_ln_p<false>(c, acc, T1, g0, be0, a.eps, off, T0, T2, red2, a.rstd0);      // xhat0 -> the A tile, out0 -> T2
@@ -479,7 +510,7 @@ __global__ __launch_bounds__(512, 1) void row_chain_pipe_kernel(ChainArgs a) {
   if (FFN) {
     const int dff = nc * 256;
     f32x16 acc1[MT], acc2[MT];
-    acc_init(acc2, nb2);
+    acc_init(acc2, nb2, pb2);
     acc_init(acc1, nb1);
     if (nc > 1) bias_load(c, a.b1 + 256, nb1);
     auto bits_at = [&](int ch) {

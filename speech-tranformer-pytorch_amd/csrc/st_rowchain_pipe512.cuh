@@ -39,8 +39,13 @@ __device__ __forceinline__ void tile5_store(const Ctx<2>& c, const Tile5Regs& t,
   }
 }
 
-// LayerNorm over 512 columns: acc[h] (bias inside) + res; each wave holds 2 x 32 columns of every row.  As epi_ln_p.
-template <bool DROP>
+// LayerNorm over 512 columns: acc[h] (bias - bias[0] inside) + res; each wave holds 2 x 32 columns of every row.  As epi_ln_p: one
+// pass over the distances from the row's pivot bias[0] + res[row][0].  RPIV = false: the accumulators already hold acc - pivot
+// (acc_init_pivot: the second LayerNorm).  What the pivot costs this kernel: 236 -> 244 VGPRs without the projection; with it (at the
+// 256-register limit either way) 12 -> 16 bytes of scratch per lane, 32 -> 60 with dropout; per step of BASELINE config 3 nothing
+// beyond the spread of two runs of one build (profiles/ln_stats_bench.json; with the second LayerNorm's residual pivot subtracted in
+// the epilogue it was +0.014 ms of 11.2 and outside that spread in two rounds of three).
+template <bool DROP, bool RPIV = true>
 __device__ __forceinline__ void epi_ln512_p(const Ctx<2>& c, f32x16 (&acc)[2][2], const bf16* res, const BiasRegs (&gamma)[2],
                                             const BiasRegs (&beta)[2], float eps, const Drop& d, bf16* t_xhat, bf16* t_out, float* red2,
                                             float* g_rstd) {
@@ -53,6 +58,9 @@ __device__ __forceinline__ void epi_ln512_p(const Ctx<2>& c, f32x16 (&acc)[2][2]
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         rr[h][mt][g] = *reinterpret_cast<const bf16x4*>(res + (mt * 32 + c.r) * PT5 + h * 256 + c.wave * 32 + 8 * g + 4 * c.hi);
+  float pv[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) pv[mt] = RPIV ? (float)res[(mt * 32 + c.r) * PT5] : 0.f;      // (false: acc_init_pivot took it)
   float s[MT], q[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
@@ -63,7 +71,7 @@ __device__ __forceinline__ void epi_ln512_p(const Ctx<2>& c, f32x16 (&acc)[2][2]
       for (int g = 0; g < 4; ++g)
 #pragma unroll
         for (int e = 0; e < 4; e += 2) {
-          const float v0 = acc[h][mt][4 * g + e] + (float)rr[h][mt][g][e], v1 = acc[h][mt][4 * g + e + 1] + (float)rr[h][mt][g][e + 1];
+          const float v0 = acc[h][mt][4 * g + e] + ((float)rr[h][mt][g][e] - pv[mt]), v1 = acc[h][mt][4 * g + e + 1] + ((float)rr[h][mt][g][e + 1] - pv[mt]);
           acc[h][mt][4 * g + e] = v0;
           acc[h][mt][4 * g + e + 1] = v1;
           s0 += v0; s1 += v1;
@@ -91,7 +99,7 @@ __device__ __forceinline__ void epi_ln512_p(const Ctx<2>& c, f32x16 (&acc)[2][2]
   for (int mt = 0; mt < MT; ++mt) {
     const float ss = (pp[mt][0][0] + pp[mt][0][2]) + (pp[mt][1][0] + pp[mt][1][2]) + ((pp[mt][2][0] + pp[mt][2][2]) + (pp[mt][3][0] + pp[mt][3][2]));
     const float qq = (pp[mt][0][1] + pp[mt][0][3]) + (pp[mt][1][1] + pp[mt][1][3]) + ((pp[mt][2][1] + pp[mt][2][3]) + (pp[mt][3][1] + pp[mt][3][3]));
-    const float mean = ss * (1.f / DM5);
+    const float mean = ss * (1.f / DM5);      // (of the distances from the pivot)
     const float var = fmaxf(qq * (1.f / DM5) - mean * mean, 0.f);
     rstd[mt] = rsqrtf(var + eps);
     nm[mt] = -mean * rstd[mt];
@@ -167,6 +175,7 @@ __global__ __launch_bounds__(512, 1) void row_chain512_kernel(ChainArgs a) {
     tile5_load(c, a.A, a.lda, ra);
     bias_load(c, a.bo, bo[0]);
     bias_load(c, a.bo + 256, bo[1]);
+    const float pb0 = a.bo[0];                // the bias part of the LayerNorm's pivot (epi_ln512_p): asked for with the vector
     tile5_store(c, ra, TA);
     __builtin_amdgcn_sched_barrier(0);
     tile5_load(c, a.R, a.ldr, rr);            // (asked for once A is here: st_rowchain_pipe.cuh)
@@ -176,8 +185,8 @@ __global__ __launch_bounds__(512, 1) void row_chain512_kernel(ChainArgs a) {
       bias_load(c, a.be0 + h * 256, be0[h]);
     }
     __syncthreads();
-    acc_init(acc2[0], bo[0]);
-    acc_init(acc2[1], bo[1]);
+    acc_init(acc2[0], bo[0], pb0);
+    acc_init(acc2[1], bo[1], pb0);
     block_mma_pt<PT5>(c, blk(0), blk(1), TA, acc2[0], ns);
     tile5_store(c, rr, TB);                   // the residual arrived under the block
     block_mma_pt<PT5>(c, blk(1), blk(2), TA + 256, acc2[0], ns);
@@ -197,6 +206,7 @@ __global__ __launch_bounds__(512, 1) void row_chain512_kernel(ChainArgs a) {
     BiasRegs b2[2];
     bias_load(c, a.b2, b2[0]);
     bias_load(c, a.b2 + 256, b2[1]);
+    const float pb2 = a.b2[0];
     acc_init(acc1, nb1);
     if (nc > 1) bias_load(c, a.b1 + 256, nb1);
     {       // W1_0: its two blocks carry the copies of xhat0 (TA) and out0 (TB)
@@ -207,8 +217,8 @@ __global__ __launch_bounds__(512, 1) void row_chain512_kernel(ChainArgs a) {
       CopySide<MT, 2> cs{c, {desc(TB, a.out0, DM5), desc(TB + 256, a.out0 ? a.out0 + 256 : nullptr, DM5)}};
       block_mma_pt<PT5>(c, W1(0, 1), nc > 1 ? W1(1, 0) : W2(0, 0), cur + 256, acc1, cs);
     }
-    acc_init(acc2[0], b2[0]);
-    acc_init(acc2[1], b2[1]);
+    acc_init_pivot(c, acc2[0], b2[0], pb2, cur, PT5);      // (cur = out0, complete: the second LayerNorm's whole pivot)
+    acc_init_pivot(c, acc2[1], b2[1], pb2, cur, PT5);
   }
   __syncthreads();        // every wave is past its copies of xhat0: TA's halves take the hidden chunks
   {
@@ -249,7 +259,7 @@ __global__ __launch_bounds__(512, 1) void row_chain512_kernel(ChainArgs a) {
     }
     block_mma_pt<PT5>(c, W2(nc - 1, 1), PB(0, 0), hl, acc2[1], ns);
     __syncthreads();      // every wave is past its MFMAs on and its copy of the last chunk: TA takes xhat1
-    epi_ln512_p<DROP>(c, acc2, cur, g1, be1, a.eps, d2, TA, cur, red2, a.rstd1);      // xhat1 -> TA, out1 replaces cur in place
+    epi_ln512_p<DROP, false>(c, acc2, cur, g1, be1, a.eps, d2, TA, cur, red2, a.rstd1);      // xhat1 -> TA, out1 replaces cur in place
     __syncthreads();
   }
 

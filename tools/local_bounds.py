@@ -2,7 +2,8 @@
 tests/_emul.py evaluated with fp32 and with fp64 accumulation - same bf16 rounding points - over the kernel tests' own cases;
 the largest per-row / per-column / per-element ratio of tests/_local.py per family and output; likewise the slow-path attention
 kernels over the cases of tests/test_slow_attention_gpu.py (families "dense" and "probs") and the fast attention kernels at sharp
-scores over the cases of tests/test_sharp_attention_gpu.py (family "sharp").  No kernel runs here.
+scores over the cases of tests/test_sharp_attention_gpu.py (family "sharp"); the LayerNorm statistic off centre, at tiny spread and on
+constant rows over the cases of tests/test_ln_stats_gpu.py (family "ln_stats").  No kernel runs here.
 
     python tools/local_bounds.py            # prints one line per family / output
 """
@@ -19,6 +20,7 @@ for p in (ROOT, os.path.join(ROOT, "speech-tranformer-pytorch_amd")):
 
 from st_amd import chains, native as nv          # noqa: E402
 from tests import _emul as em                     # noqa: E402
+from tests import _ln_stats as ls                 # noqa: E402
 from tests import _sharp_attn as sh               # noqa: E402
 from tests import _slow_attn as sa                # noqa: E402
 from tests import test_kernels_gpu as tk          # noqa: E402
@@ -206,6 +208,23 @@ def sharp():
                 note(fam + " (bf16 vs fp64)", nm, a, c.ref[nm].float(), rows=rows)
 
 
+def ln_stats():
+    """The LayerNorm kernels over the cases of tests/test_ln_stats_gpu.py (tests/_ln_stats.py), per row family: the fp32 emulation
+    against the UNROUNDED fp64 reference of tests/_ln_ref.py - rstd as the worst |got / ref - 1| over all rows, implementations'
+    shapes and both LayerNorms of a chain (the figure L_RSTD = 1e-4 leaves room above), xhat / out as the worst row: the room the
+    one rounding takes of L_BF16."""
+    import contextlib
+    import io
+    for _, kw in ls.cases():
+        report = []
+        with contextlib.redirect_stdout(io.StringIO()):        # (the checks print every figure)
+            ls.run(kw, ls.CPU, report=report)
+        for _, _, f, xh, o, _ in report:
+            for nm, axis, v in (("rstd", "element", f), ("xhat", "row", xh), ("out", "row", o)):
+                key = ("ln_stats %s" % kw["family"], nm, axis)
+                worst[key] = max(worst.get(key, 0.0), v)
+
+
 def probs():
     """st_attn_probs over the cases of tests/test_slow_attention_gpu.py: the emulation's fp32 maps against the fp64 reference."""
     for kw in sa.probs_cases():
@@ -259,6 +278,7 @@ if __name__ == "__main__":
     dense()
     probs()
     sharp()
+    ln_stats()
     losses()
     for (family, name, axis), v in sorted(worst.items()):
         print("%-28s %-8s %-8s worst ratio %.3e   x3 = %.3e" % (family, name, axis, v, 3 * v))
