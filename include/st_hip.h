@@ -41,7 +41,7 @@ typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C:
  * ST_EPI_* values; comments, whitespace, parameter names and `const` do not count), computed by native.abi_fingerprint():
  *   change a declaration - importing st_amd.native fails - paste the number its message prints.
  * So it cannot be forgotten, and there is nothing in it to assert by value: no test may spell it out. */
-#define ST_ABI_VERSION 1713104753
+#define ST_ABI_VERSION 1664642158
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -587,6 +587,22 @@ int st_ctc_loss_fwd(st_stream_t stream, const float* lp, int B, int T, int C, co
 int st_ctc_loss_grad(st_stream_t stream, const float* lp, int B, int T, int C, const long long* classes, int L, const int* in_len,
                      const int* tgt_len, const float* coef, void* ws, long long ws_bytes, const float* nll, float* g, float* roww,
                      int softmax_term);
+
+/* CTC forced alignment (csrc/st_ctc_align.hip): the Viterbi (best-path) alignment of the labels through the same lattice, on the
+ * inputs of st_ctc_loss_fwd (lp need not be normalised: plain numbers; nothing is read from host memory, so the launch can be
+ * captured).  v_0(0) = lp_0(0), v_0(1) = lp_0(c_0); v_t(s) = lp_t(l'(s)) + max(v_{t-1}(s), v_{t-1}(s-1), [l'(s) != l'(s-2)]
+ * v_{t-1}(s-2)) in fp32, natural units, the wave maximum subtracted every 8 frames (integer-valued lp: every operation exact).
+ * TIE RULE: predecessors are tried in the order stay, s-1, s-2, a later one wins only if strictly greater; the end state is the
+ * last blank S-1 unless the last label S-2 is strictly better.
+ * path i32 [B, T]: for t < in_len[b] the label position j in [0, tl) whose label state emits frame t, -1 for a blank state (a
+ * label equal to class 0 is a label); -1 at and past in_len[b].  spans i32 [B, L, 2]: [start, end) frames of label position j
+ * (contiguous, at least one frame), (-1, -1) for j >= tl.  score f32 [B]: the sum of lp along the path, accumulated in fp64 and
+ * rounded once.  No alignment (in_len = 0, in_len < tl + adjacent repeats): score -inf, path and spans all -1.  Every byte of the
+ * three outputs is written.  ws: st_ctc_align_ws_kib(B, T, L) KiB (host query, no launch; -1: unsupported; 0 when every frame count
+ * fits the LDS copy of the back-pointers: 2,048 frames for L <= 127, 1,024 above), 16-byte aligned. */
+int st_ctc_align_ws_kib(int B, int T, int L);
+int st_ctc_align(st_stream_t stream, const float* lp, int B, int T, int C, const long long* classes, int L, const int* in_len,
+                 const int* tgt_len, void* ws, long long ws_bytes, int* path, int* spans, float* score);
 
 /* Attention probabilities of ONE attention sublayer, materialised (reference transformer/Attention.py:89,96: the `attns`
  * MultiHeadAttention.forward returns; Models.py:53-54,107-109 collect them under return_attns): P (f32 [B, H, Lq, Lk],

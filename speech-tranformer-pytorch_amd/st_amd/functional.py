@@ -677,6 +677,15 @@ class CtcPlan:
             self.ws = torch.empty(nv.ctc_loss_ws_bytes(self.B, self.T, self.L), dtype=torch.uint8, device=self.lp.device)
         return self.ws
 
+    def align_workspace(self):
+        """The back-pointer workspace of the forced alignment (native.ctc_align; empty while every frame count fits the kernel's
+        LDS copy), allocated on first use - like loss_workspace, never inside a capture."""
+        if getattr(self, "align_ws", None) is None:
+            if self.lp.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("CtcPlan.align_workspace: first use inside a stream capture - call it before capturing")
+            self.align_ws = torch.empty(nv.ctc_align_ws_bytes(self.B, self.T, self.L), dtype=torch.uint8, device=self.lp.device)
+        return self.align_ws
+
     def refresh_labels(self, targets) -> None:
         """(Re)derive everything that depends on the label VALUES, written in place: a loader that refills the same static
         target buffer with new labels of the same lengths keeps its batch signature (addresses, shapes, lengths), so

@@ -1075,6 +1075,57 @@ def ctc_loss_grad(lp, classes, in_len, tgt_len, coef, ws, nll, g, roww, softmax_
     return g
 
 
+# ---- CTC forced alignment (csrc/st_ctc_align.hip) ---------------------------------------------------------------------------------
+def ctc_align_ws_bytes(B, T, L) -> int:
+    """Bytes of the back-pointer workspace st_ctc_align wants for lp [B, T, *] and classes [B, L] (a host-only query: no launch,
+    no GPU) - 0 while every frame count fits the kernel's LDS copy (2,048 frames for L <= 127, 1,024 above)."""
+    if L > CTC_LOSS_MAX_L or min(B, T, L) < 0:
+        raise ValueError("ctc_align: at most %d labels per utterance are supported (got L = %d)" % (CTC_LOSS_MAX_L, L))
+    kib = int(load()._cdll.st_ctc_align_ws_kib(int(B), int(T), int(L)))
+    if kib < 0:
+        raise ValueError("st_ctc_align_ws_kib: unsupported shape B = %d, T = %d, L = %d" % (B, T, L))
+    return kib * 1024
+
+
+def ctc_align(lp, classes, in_len, tgt_len, ws, path, spans, score):
+    """The Viterbi alignment of ``classes`` through lp (the inputs of ctc_loss_fwd; lengths are DEVICE i32 tensors: capturable):
+    path i32 [B, T] (label position per frame, -1 = blank or past the length), spans i32 [B, L, 2] ([start, end) frames of every
+    label position, (-1, -1) past tgt_len), score f32 [B] (sum of lp along the path; -inf and all -1 where no alignment exists)
+    - see st_ctc_align for the recursion and its tie rule.  ws: a flat uint8 buffer of ctc_align_ws_bytes(B, T, L)."""
+    who = "ctc_align"
+    if lp.dim() != 3 or lp.dtype != F32 or not lp.is_contiguous():
+        raise ValueError("%s: lp must be a contiguous f32 [B, T, C] tensor, got %s %s" % (who, lp.dtype, tuple(lp.shape)))
+    B, T, C = lp.shape
+    if C < 2:
+        raise ValueError("%s: lp needs at least two classes (blank + one label), got C = %d" % (who, C))
+    if T < 1:
+        raise ValueError("%s: lp has no frames" % who)
+    if classes.dim() != 2 or classes.shape[0] != B or classes.dtype != I64 or not classes.is_contiguous():
+        raise ValueError("%s: classes must be a contiguous i64 [B, L] tensor, got %s %s" % (who, classes.dtype, tuple(classes.shape)))
+    L = classes.shape[1]
+    if L > CTC_LOSS_MAX_L:
+        raise ValueError("%s: at most %d labels per utterance are supported (got L = %d)" % (who, CTC_LOSS_MAX_L, L))
+    for name, t, dtype, shape in (("in_len", in_len, I32, (B,)), ("tgt_len", tgt_len, I32, (B,)), ("path", path, I32, (B, T)),
+                                  ("spans", spans, I32, (B, L, 2)), ("score", score, F32, (B,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s %s tensor, got %s %s" % (who, name, dtype, list(shape), t.dtype, tuple(t.shape)))
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous():
+        raise ValueError("%s: ws must be a flat uint8 buffer (native.ctc_align_ws_bytes)" % who)
+    need = ctc_align_ws_bytes(B, T, L)         # (a host-only query)
+    if ws.numel() < need:
+        raise ValueError("%s: ws holds %d bytes, %d are needed" % (who, ws.numel(), need))
+    for name, t in (("lp", lp), ("classes", classes), ("in_len", in_len), ("tgt_len", tgt_len), ("ws", ws), ("path", path),
+                    ("spans", spans), ("score", score)):
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s must live on the GPU: the HIP path has no CPU fallback" % (who, name))
+    if need and ws.data_ptr() % 16:
+        raise ValueError("%s: ws must be 16-byte aligned" % who)
+    _tag("ctc_align", B, T, L, io=(lp, path, spans))
+    _check(load().st_ctc_align(_stream(), lp.data_ptr(), B, T, C, classes.data_ptr(), L, in_len.data_ptr(), tgt_len.data_ptr(),
+                               ws.data_ptr(), ws.numel(), path.data_ptr(), spans.data_ptr(), score.data_ptr()), "st_ctc_align")
+    return path, spans, score
+
+
 def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False, out=None):
     """The attention probabilities of one sublayer, materialised: f32 [B, n_head, Lq, Lk] (zeros at masked keys and in the
     rows of padding positions).  Q, K: bf16 row matrices (column slices of the q | k | v projection are fine).  out: the

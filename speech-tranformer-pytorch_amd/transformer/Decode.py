@@ -56,7 +56,8 @@ class Decode(object):
         ug = getattr(opt, "use_graph", None)
         self.use_graph = torch.device(device).type == "cuda" if ug is None else bool(ug)
         self._side = None
-        self._warm = False        # a step has run eagerly on this object: later calls capture before their step 0
+        self.alignment = None     # align(): the device tensors of its last call
+        self._warm = False       # a step has run eagerly on this object: later calls capture before their step 0
 
     # ---- one decoder step for all n = B * beam hypotheses; everything that changes from step to step is DEVICE state ---
     @torch.no_grad()
@@ -306,6 +307,64 @@ class Decode(object):
                 prev = k
             out.append(labels)
             o += int(T)
+        return out
+
+    @torch.no_grad()
+    def align(self, src_batch, hyps, strip_eos=True):
+        """CTC forced alignment of ONE token list per utterance (``hyps[b]``, e.g. ``decode_batch(...)[0][b][0]``) with the CTC
+        head: WHEN each token was spoken.  -> a list of B pairs ``(items, score)``: ``items`` = one ``(token, start, end, logp)``
+        per token - the token occupies the encoder rows [start, end) of its utterance (contiguous, at least one row, in order),
+        ``logp`` = the sum of the head's log-probabilities of the token over its own rows (a per-token confidence) - and
+        ``score`` = the log-probability of the whole best path (blank rows included).  An utterance whose rows cannot spell its
+        tokens (fewer rows than tokens + adjacent repeats) returns ``([], -inf)``.
+
+        Rows and time: row t stands at raw feature frame ``t * interval``, i.e. at ``t * interval * 10 ms`` for 10 ms frames,
+        ``interval`` as in ``st_amd.features.stack_frames`` (1 without frame stacking).
+
+        ``strip_eos=True`` drops one trailing EOS (the prefix scorer's convention: EOS is not a CTC label); ``strip_eos=False``
+        aligns the closing token as a label (the convention of JointTrainStep's labels).  ValueError: no CTC head, a leading BOS,
+        a token outside the vocabulary, more than 255 labels.  One encoder pass, one st_ctc_align launch and one host read per
+        batch (st_amd.ctc_align)."""
+        from st_amd import ctc_align
+        if self.ctc_head is None:
+            raise ValueError("align: needs the CTC head (Decode(..., ctc_head=...))")
+        inputs, in_len = src_batch
+        B, V = inputs.shape[0], self.model.vocab_size
+        if len(hyps) != B:
+            raise ValueError("align: %d token lists for %d utterances" % (len(hyps), B))
+        labs = []
+        for b, h in enumerate(hyps):
+            h = [int(k) for k in h]
+            if h and h[0] == Constants.BOS:
+                raise ValueError("align: utterance %d starts with BOS - pass the tokens after it" % b)
+            if strip_eos and h and h[-1] == Constants.EOS:
+                h = h[:-1]
+            if any(k < 0 or k >= V for k in h):
+                raise ValueError("align: utterance %d has a token outside the vocabulary [0, %d)" % (b, V))
+            if len(h) > nv.CTC_LOSS_MAX_L:
+                raise ValueError("align: utterance %d has %d labels, at most %d are supported" % (b, len(h), nv.CTC_LOSS_MAX_L))
+            labs.append(h)
+        L = max(1, max(len(h) for h in labs))
+        labels = torch.zeros(B, L, dtype=torch.long)
+        for b, h in enumerate(labs):
+            labels[b, :len(h)] = torch.tensor(h, dtype=torch.long)
+        lengths = torch.tensor([len(h) for h in labs], dtype=torch.long)
+        model, dev = self.model, self.device
+        inputs = inputs.to(dev)
+        t_max = int(in_len.max())
+        with arena_of(model).scope():
+            enc, in_rows = model.encoder.forward_rows(inputs[:, :t_max], in_len)
+            al = ctc_align.align_rows(self.ctc_head, enc, in_rows, labels.to(dev), lengths)
+            host = torch.cat([al.spans.reshape(B, 2 * L).double(), al.token_logp.double(), al.score.double().unsqueeze(1)], 1).cpu()
+        self.alignment = al        # the device tensors of the last call (st_amd.ctc_align.Alignment: the per-row path, lp, classes)
+        out = []
+        for b, h in enumerate(labs):
+            row = host[b].tolist()
+            score = row[3 * L]
+            if score == float("-inf"):
+                out.append(([], score))
+                continue
+            out.append(([(k, int(row[2 * j]), int(row[2 * j + 1]), row[2 * L + j]) for j, k in enumerate(h)], score))
         return out
 
     def _decode_batch(self, src_batch):
