@@ -2,7 +2,8 @@
 
 What a recipe reports per epoch - and picks checkpoints, stops early and chooses between raw and averaged weights by - is the
 criterion's value, the plain token-mean NLL (perplexity) and the share of positions whose arg-max is the ground truth, all
-under teacher forcing.  ``EvalStep`` computes them the way ``TrainStep`` computes a step: ``model.forward_packed`` leaves the
+under teacher forcing.  ``EvalStep`` computes them on the path a training step takes (the shared driver pieces - bucket staging,
+capture, replay - are st_amd/stepdriver.py): ``model.forward_packed`` leaves the
 logits in the ragged ``[rows, v_pad]`` layout, ``st_ce_eval_fwd`` reads every row once (loss numerator, NLL, arg-max hit) and
 ``st_eval_note`` adds the batch into an fp64 accumulator in device memory.  Nothing is scattered to ``[B, L, V]``, nothing is
 saved for a backward, the optimizer and the dropout seed are never touched, and the host reads ONE tensor per pass::
@@ -22,11 +23,11 @@ from __future__ import annotations
 import math
 
 import torch
-import torch.distributed
 
 from . import native as nv
-from .functional import TailBuffers, ce_spec
-from .trainer import no_gc_inside_capture, stage_bucket
+from .functional import ce_spec
+from .stepdriver import (LossDenom, bucket_step, capture_kwargs, no_gc_inside_capture, parse_buckets, prepare_capture,
+                         stage_bucket, trim_batch, zero_tails)
 
 
 class _Cap:
@@ -61,15 +62,10 @@ class EvalStep:
             raise ValueError("EvalStep: use_graph=True needs bucket=(T_cap, L_cap) - the batches of a dev set do not repeat a "
                              "length signature, so only a bucket capture is ever replayed (or pass use_graph=False)")
         self.use_graph, self.graph_warmup = bool(use_graph), int(graph_warmup)
-        self.bucket = None if bucket is None else (int(bucket[0]), int(bucket[1]))
-        if bucket_rows is not None and not isinstance(bucket_rows[0], (tuple, list)):
-            bucket_rows = [bucket_rows]
-        self.bucket_rows = None if bucket_rows is None else [(int(a), int(b)) for a, b in bucket_rows]
-        if self.bucket_rows is not None and self.bucket is None:
-            raise ValueError("EvalStep: bucket_rows needs bucket=(T_cap, L_cap)")
+        self.bucket, self.bucket_rows = parse_buckets("EvalStep", bucket, bucket_rows)
         self._buckets = {}
         self.acc = self.last = None
-        self._denom, self._denom_host = None, None
+        self._denom = LossDenom()       # the loss denominator of a "rows" / "sum" criterion, staged per batch
 
     # ---- device state -----------------------------------------------------------------------------------------------------
     def _state(self, device) -> None:
@@ -79,18 +75,6 @@ class EvalStep:
             self.last = torch.zeros(4, dtype=torch.float32, device=device)
         elif self.acc.device != device:
             raise RuntimeError("EvalStep: the accumulator lives on %s, this batch on %s" % (self.acc.device, device))
-
-    def _stage_denom(self, B: int, l_max: int, device) -> None:
-        """The loss denominator of a "rows" / "sum" criterion: a device scalar the kernel reads at run time, refreshed per batch
-        by an eager fill (never inside a capture), so one captured forward serves batches whose l_max differ."""
-        if self.norm == "tokens":
-            return
-        d = float(B * l_max) if self.norm == "rows" else 1.0
-        if self._denom is None:
-            self._denom = torch.full((1,), d, dtype=torch.float32, device=device)
-        elif d != self._denom_host:
-            self._denom.fill_(d)
-        self._denom_host = d
 
     def reset(self) -> None:
         """A new pass: the accumulator back to zero, in place."""
@@ -112,35 +96,29 @@ class EvalStep:
 
     # ---- one batch ----------------------------------------------------------------------------------------------------------
     def _forward(self, inputs, input_lengths, targets, target_lengths, ground_truth, layouts=None):
-        tb = TailBuffers.active
-        if tb is not None and tb.mode == "serve" and tb.bufs:      # (a captured packed bucket: the unassigned tail rows, one launch)
-            nv.zero_tails(tb.table, TailBuffers.N_MAX)
+        zero_tails()
         with torch.no_grad():
             # the whole [rows, v_pad] buffer, padding columns at -1e30; the kernel reads the first vocab_size columns
             logits, t_rows = self.model.forward_packed(inputs, input_lengths, targets, target_lengths, padded_logits=True,
                                                        layouts=layouts)
             # (a 1-D ground truth is the padded [B, L_cap] one flattened, with a spare ignored element behind it for the
-            # rows a packed bucket leaves unassigned: trainer.stage_bucket)
+            # rows a packed bucket leaves unassigned: stepdriver.stage_bucket)
             L_gt = ground_truth.shape[1] if ground_truth.dim() == 2 else t_rows.max_len
             rows = torch.empty(logits.shape[0], 4, dtype=torch.float32, device=logits.device)
             c, s, z = self._triple
             nv.ce_eval_fwd(logits, ground_truth.contiguous().view(-1), 0, c, s, z, rows, V=self.vocab_size,
                            index=t_rows.scatter_index(L_gt))
-            nv.eval_note(rows, self.acc, self.last, denom=self._denom)
+            nv.eval_note(rows, self.acc, self.last, denom=self._denom.tensor)
         return self.last
 
     def _capture(self, batch, layouts):
-        dev = batch[0].device
+        prepare_capture(batch[0].device)
         with no_gc_inside_capture():
-            nv.splitk_scratch(dev)          # process-wide scratch exists before any capture (trainer.TrainStep._capture_graphs)
-            torch.cuda.synchronize()
             cap = _Cap()
             cap.graph = torch.cuda.CUDAGraph()
-            # the captured kernels read the layouts and the staging buffers by address
-            cap.keep = (layouts, batch[0], batch[2], batch[4], TailBuffers.active)
-            # (with a process group alive its watchdog thread polls events: only this thread's calls are policed)
-            mode = dict(capture_error_mode="thread_local") if torch.distributed.is_initialized() else {}
-            with torch.cuda.graph(cap.graph, pool=torch.cuda.graph_pool_handle(), **mode):
+            # the captured kernels read the layouts and the staging buffers by address (the served tail buffers: the bucket's)
+            cap.keep = (layouts, batch[0], batch[2], batch[4])
+            with torch.cuda.graph(cap.graph, pool=torch.cuda.graph_pool_handle(), **capture_kwargs()):
                 self._forward(*batch, layouts=layouts)
         return cap          # capture only records: the replay that follows runs the batch
 
@@ -150,33 +128,17 @@ class EvalStep:
         if any(m.training for m in self.model.modules()):
             raise RuntimeError("EvalStep: the model (or one of its modules) is in training mode - dropout and SpecAugment would "
                                "mask the validation pass; call model.eval() first")
-        t_max, l_max = int(input_lengths.max()), int(target_lengths.max())
-        batch = (inputs[:, :t_max], input_lengths, targets[:, :l_max], target_lengths, ground_truth[:, :l_max])
+        batch = trim_batch(inputs, input_lengths, targets, target_lengths, ground_truth)
         self._state(inputs.device)
-        self._stage_denom(batch[4].shape[0], batch[4].shape[1], inputs.device)
+        self._denom.stage(self.norm, batch[4].shape[0], batch[4].shape[1], inputs.device)
         if self.bucket is None:
             return self._forward(*batch)
         st, batch, packed = stage_bucket("EvalStep", self.model, self._buckets, self.bucket, self.bucket_rows, *batch)
         if not self.use_graph:
             return self._forward(*batch, layouts=st.layouts)
-        if st.cap is None:
-            st.seen += 1
-            if st.seen <= self.graph_warmup:
-                if packed and st.seen == self.graph_warmup:
-                    # the last eager batch notes the buffers whose unassigned tail rows must read as zeros; the capture serves
-                    # them from persistent memory and zeroes all tails with one launch (functional.TailBuffers)
-                    st.tails = TailBuffers()
-                    TailBuffers.active = st.tails
-                    try:
-                        return self._forward(*batch, layouts=st.layouts)
-                    finally:
-                        TailBuffers.active = None
-                return self._forward(*batch, layouts=st.layouts)
-            if packed and st.tails is not None:
-                TailBuffers.active = st.tails.materialize(inputs.device)
-            try:
-                st.cap = self._capture(batch, st.layouts)
-            finally:
-                TailBuffers.active = None
-        st.cap.graph.replay()
+        return bucket_step(st, packed, self.graph_warmup, lambda: self._forward(*batch, layouts=st.layouts),
+                           lambda: self._capture(batch, st.layouts), self._replay, serve_tails=True)
+
+    def _replay(self, cap):
+        cap.graph.replay()
         return self.last

@@ -30,12 +30,14 @@ step on their concatenation would compute.  Every micro-batch adds the gradient 
 denominator (the window's token count, say) is summed on the device and applied once, inside the norm and the clip + Adam
 kernels of the update (st_grad_norm, st_adam_clip with their win pointer) - no host read, and the update kernel leaves the buffer zeroed for
 the next window.  In graph mode the micro-batch and the update are two captures.
+
+What the drivers here share with each other and with the validation driver - batch trimming and signatures, the loss
+denominator, the preparation of a capture, bucket staging and the bucket's warm-up / capture / replay runner - is
+st_amd/stepdriver.py; this file keeps each driver's own policy (and re-exports the names tests and tools import from here).
 """
 from __future__ import annotations
 
 import collections
-import contextlib
-import gc
 import os
 import time
 from typing import Optional
@@ -48,26 +50,10 @@ from .arena import arena_of
 from .dp import GradReducer
 from . import rng
 from . import native as nv
-from .functional import CeSpec, TailBuffers, ce_spec, deferred_wgrads
-
-
-@contextlib.contextmanager
-def no_gc_inside_capture():
-    """Around the captures of a step: collect garbage BEFORE them and keep the collector off until they have ended.
-
-    A generational pass that happens to fire inside ``with torch.cuda.graph(...)`` runs destructors in the middle of a stream
-    capture - those of a dead TrainStep's graphs and private pool, say, left in a reference cycle by an earlier step object
-    - and the process aborted there (main thread, inside the collector, inside the micro-batch capture).  torch.cuda.graph used
-    to call gc.collect() on entry; it no longer does unless torch.compiler.config.force_cudagraph_gc is set, so when a pass
-    fires is a matter of how many objects the process happens to have allocated."""
-    gc.collect()
-    was_on = gc.isenabled()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was_on:
-            gc.enable()
+from .functional import CeSpec, ce_spec, deferred_wgrads
+from .stepdriver import (LossDenom, _Bucket, batch_signature, bucket_step, capture_kwargs,  # noqa: F401  (re-exported)
+                         no_gc_inside_capture, optimizer_options, parse_buckets, prepare_capture, stage_bucket, trim_batch,
+                         zero_tails)
 
 
 def clip_grad_norm_flat(arena, max_norm: float) -> torch.Tensor:
@@ -122,9 +108,8 @@ class TrainStep:
         # resolved once: a model without forward_packed runs self.crit itself on the padded logits (any criterion will do)
         self.ce_spec = ce_spec(criterion, vocab_size) if hasattr(model, "forward_packed") else None
         # the denominator of a CeSpec with norm "rows" (B * l_max of the trimmed batch) / "sum" (1): a persistent device
-        # scalar the kernels read at run time - staged per batch, never inside a capture, so one captured step serves
-        # batches whose l_max differ
-        self._ce_denom, self._ce_denom_host = None, None
+        # scalar the kernels read at run time (stepdriver.LossDenom; read back as self._ce_denom)
+        self._denom = LossDenom()
         self.nll = None
         self.reducer = reducer
         self.global_step = 0
@@ -139,18 +124,13 @@ class TrainStep:
         # target tokens - the batch is staged into static padded buffers, the lengths live on the device (Rows.bucket), so
         # a loader whose batches never repeat a length signature still replays a graph.  Costs the padding rows
         # (B * T_cap instead of sum(len) rows through the row-wise kernels): for length-bucketed loaders.
-        self.bucket = None if bucket is None else (int(bucket[0]), int(bucket[1]))
         # bucket_rows = (input rows, target rows): the bucket's layouts are PACKED into that many rows (Rows.bucket(rows=...)) -
         # offsets on the device as well - so the captured step runs over about the batch's real row count instead of
         # B * T_cap.  Several capacities may be given, [(rows, rows), ...] in ascending order: a batch takes the first one it
         # fits (one capture each); a batch with more rows than the largest takes the padded bucket.  Pick the capacities
         # from the loader's length statistics AND the kernels' tile rounds: the encoder-sized row chains run one 96-row
         # workgroup per CU, so 256 x 96 = 24,576 rows are one round and 24,577 are two (of 64-row workgroups: up to 32,768).
-        if bucket_rows is not None and not isinstance(bucket_rows[0], (tuple, list)):
-            bucket_rows = [bucket_rows]
-        self.bucket_rows = None if bucket_rows is None else [(int(a), int(b)) for a, b in bucket_rows]
-        if self.bucket_rows is not None and self.bucket is None:
-            raise ValueError("TrainStep: bucket_rows needs bucket=(T_cap, L_cap)")
+        self.bucket, self.bucket_rows = parse_buckets("TrainStep", bucket, bucket_rows)
         self._buckets = {}
         self._graphs = collections.OrderedDict()      # signature -> captured step (LRU)
         self._seen = collections.OrderedDict()        # signature -> eager sightings before the capture
@@ -183,31 +163,17 @@ class TrainStep:
                 reducer.detach()                                     # nothing is exchanged before the update
 
     def _options(self):
-        """The optimizer's option token (None for an optimizer without options); raises inside ``optimizer.averaged()``."""
-        if getattr(self.optimizer, "_in_averaged", False):
-            raise RuntimeError("%s: called inside optimizer.averaged() - the model holds the averaged weights"
-                               % type(self).__name__)
-        token = getattr(self.optimizer, "options_token", None)
-        return None if token is None else token()
+        return optimizer_options(self.optimizer, type(self).__name__)
+
+    @property
+    def _ce_denom(self):
+        return self._denom.tensor
 
     def _backward(self, loss):
         """loss.backward() with a resident gradient seed (autograd's own ones_like(loss) is a fill launch per step)."""
         if self._seed is None or self._seed.device != loss.device or self._seed.dtype != loss.dtype:
             self._seed = torch.ones((), dtype=loss.dtype, device=loss.device)
         torch.autograd.backward(loss, grad_tensors=self._seed)
-
-    def _stage_denom(self, B: int, l_max: int, device) -> None:
-        """Refresh the loss denominator for this batch (an eager fill on the step's stream, only when the value changes)."""
-        if getattr(self, "accumulate", None) is not None:
-            return self._stage_window(B, l_max, device)
-        if self.ce_spec is None or self.ce_spec.norm == "tokens":
-            return
-        d = float(B * l_max) if self.ce_spec.norm == "rows" else 1.0
-        if self._ce_denom is None or self._ce_denom.device != device:
-            self._ce_denom = torch.full((1,), d, dtype=torch.float32, device=device)
-        elif d != self._ce_denom_host:
-            self._ce_denom.fill_(d)
-        self._ce_denom_host = d
 
     # ---- gradient accumulation ----------------------------------------------------------------------
     def _stage_window(self, B: int, l_max: int, device) -> None:
@@ -218,7 +184,7 @@ class TrainStep:
             if self._win is None or self._win.device != device:
                 self._win = torch.zeros(4, dtype=torch.float32, device=device)        # denominator, loss sum, NLL sum, micro-batches
                 self._win_out = torch.zeros(4, dtype=torch.float32, device=device)    # what st_window_close leaves
-                self._ce_denom = torch.ones(1, dtype=torch.float32, device=device)    # the kernels' denominator: always 1
+                self._denom.tensor = torch.ones(1, dtype=torch.float32, device=device)    # the kernels' denominator: always 1
                 self._gnorm = torch.zeros((), dtype=torch.float32, device=device)
                 self.window_loss, self.window_nll = self._win_out[0], self._win_out[1]
                 self._win_rows, self._win_rows_host = None, None
@@ -236,7 +202,7 @@ class TrainStep:
     def _micro_batch(self, inputs, input_lengths, targets, target_lengths, ground_truth, layouts=None):
         """One micro-batch of a window: forward, SUM loss, its note in the window, backward ADDING into the flat buffer (no
         zero_grad, no update) -> this micro-batch's loss in its own normalisation."""
-        self._zero_tails()
+        zero_tails()
         rng.advance()
         loss, _ = self.model.forward_packed(inputs, input_lengths, targets, target_lengths, ce_truth=ground_truth, ignore_index=0,
                                             layouts=layouts, ce_spec=self._acc_spec, ce_denom=self._ce_denom)
@@ -285,22 +251,15 @@ class TrainStep:
         self._close_window()
         return self.window_loss, self._gnorm
 
-    def _accumulate_call(self, batch, inputs, input_lengths, targets, target_lengths, ground_truth):
+    def _accumulate_call(self, batch, raw):
         self.updated = False
-        loss, _ = self._dispatch(batch, inputs, input_lengths, targets, target_lengths, ground_truth)
+        loss, _ = self._dispatch(batch, raw)
         self._n_acc += 1
         if self._n_acc >= self.accumulate:
             self._close_window()
         return loss, self._gnorm
 
     # ---- the two halves of a step -------------------------------------------------------------
-    @staticmethod
-    def _zero_tails():
-        """First launch of a captured packed-bucket step: the unassigned tail rows of every registered buffer (one launch)."""
-        tb = TailBuffers.active
-        if tb is not None and tb.mode == "serve" and tb.bufs:
-            nv.zero_tails(tb.table, TailBuffers.N_MAX)
-
     def _single_graph(self) -> bool:
         """The whole step is captured as ONE graph (no data-parallel split into several captures that share a memory pool)."""
         split = self.reducer is not None and self.reducer.active and hasattr(self.model, "forward_packed") \
@@ -308,7 +267,7 @@ class TrainStep:
         return not split or self.dp_in_graph or self.accumulate is not None      # (a micro-batch is always one graph)
 
     def _forward_backward(self, inputs, input_lengths, targets, target_lengths, ground_truth, captured=False, layouts=None):
-        self._zero_tails()
+        zero_tails()
         self.optimizer.zero_grad()
         rng.advance()                          # next step's dropout masks (an in-place device add: capturable)
         if layouts is not None:
@@ -344,7 +303,7 @@ class TrainStep:
     def _forward_decoder_backward(self, inputs, input_lengths, targets, target_lengths, ground_truth, layouts=None):
         """zero_grad, forward, loss, and the backward down to the encoder output (weight gradients of the decoder
         flushed).  Leaves (encoder output, its gradient) in ``self._cut`` for :meth:`_encoder_backward`."""
-        self._zero_tails()
+        zero_tails()
         self.optimizer.zero_grad()
         rng.advance()
         loss, t_rows, enc, enc_leaf = self.model.forward_packed(inputs, input_lengths, targets, target_lengths,
@@ -440,24 +399,28 @@ class TrainStep:
     def __call__(self, inputs, input_lengths, targets, target_lengths, ground_truth):
         """inputs [B, T, F] / targets, ground_truth [B, L] on the GPU; lengths on host or GPU."""
         self._options()
-        t_max, l_max = int(input_lengths.max()), int(target_lengths.max())     # host ints when lengths are CPU tensors
-        if self.accumulate is None:
-            self.global_step += 1                # (accumulating: counted per update, in _close_window)
-        batch = (inputs[:, :t_max], input_lengths, targets[:, :l_max], target_lengths, ground_truth[:, :l_max])
-        self._stage_denom(batch[4].shape[0], batch[4].shape[1], inputs.device)      # (label smoothing, norm "rows": B * l_max)
+        raw = (inputs, input_lengths, targets, target_lengths, ground_truth)
+        batch = trim_batch(*raw)
+        B, l_max = batch[4].shape
         if self.accumulate is not None:
-            return self._accumulate_call(batch, inputs, input_lengths, targets, target_lengths, ground_truth)
-        return self._dispatch(batch, inputs, input_lengths, targets, target_lengths, ground_truth)
+            self._stage_window(B, l_max, inputs.device)
+            return self._accumulate_call(batch, raw)
+        self.global_step += 1                    # (accumulating: counted per update, in _close_window)
+        self._denom.stage(getattr(self.ce_spec, "norm", None), B, l_max, inputs.device)      # (label smoothing, norm "rows": B * l_max)
+        return self._dispatch(batch, raw)
 
-    def _dispatch(self, batch, inputs, input_lengths, targets, target_lengths, ground_truth):
-        """Eager step, bucket step, or the captured step of this batch signature."""
+    def _dispatch(self, batch, raw):
+        """Eager step, bucket step, or the captured step of this batch signature (that of the untrimmed tensors ``raw``)."""
         if self.bucket is not None:
-            return self._bucket_call(*batch)
+            st, batch, packed = stage_bucket("TrainStep", self.model, self._buckets, self.bucket, self.bucket_rows, *batch)
+            if not self.use_graph:
+                return self._eager(batch, st.layouts)
+            return bucket_step(st, packed, self.graph_warmup, lambda: self._eager(batch, st.layouts),
+                               lambda: self._capture(batch, st.layouts), self._replay, serve_tails=self._single_graph())
         if not self.use_graph:
             return self._eager(batch)
 
-        sig = (inputs.data_ptr(), targets.data_ptr(), ground_truth.data_ptr(), tuple(inputs.shape),
-               tuple(targets.shape), input_lengths.cpu().numpy().tobytes(), target_lengths.cpu().numpy().tobytes())
+        sig = batch_signature(*raw)
         cap = self._graphs.get(sig)
         if cap is None:
             n = self._seen.get(sig, 0) + 1
@@ -473,33 +436,6 @@ class TrainStep:
                 self._graphs.popitem(last=False)         # least recently used: its graphs, pool and pinned layouts go
         self._graphs.move_to_end(sig)
         return self._replay(cap)
-
-    def _bucket_call(self, inputs, input_lengths, targets, target_lengths, ground_truth):
-        """Bucket mode: stage the batch into the bucket's static buffers, refresh the device-resident lengths, replay."""
-        st, batch, packed = stage_bucket("TrainStep", self.model, self._buckets, self.bucket, self.bucket_rows, inputs,
-                                         input_lengths, targets, target_lengths, ground_truth)
-        if not self.use_graph:
-            return self._eager(batch, layouts=st.layouts)
-        if st.cap is None:
-            st.seen += 1
-            if st.seen <= self.graph_warmup:
-                if packed and st.seen == self.graph_warmup:
-                    # the last eager step notes the buffers whose unassigned tail rows must read as zeros: the capture
-                    # serves them from persistent memory and zeroes all tails with one launch (functional.TailBuffers)
-                    st.tails = TailBuffers()
-                    TailBuffers.active = st.tails
-                    try:
-                        return self._eager(batch, layouts=st.layouts)
-                    finally:
-                        TailBuffers.active = None
-                return self._eager(batch, layouts=st.layouts)
-            if packed and st.tails is not None and self._single_graph():
-                TailBuffers.active = st.tails.materialize(inputs.device)
-            try:
-                st.cap = self._capture(batch, layouts=st.layouts)
-            finally:
-                TailBuffers.active = None
-        return self._replay(st.cap)
 
     def _replay(self, cap):
         if cap.options != self._options():
@@ -530,19 +466,10 @@ class TrainStep:
             return self._capture_graphs(batch, layouts)
 
     def _capture_graphs(self, batch, layouts=None):
-        if hasattr(self.optimizer, "_flat_state") and getattr(self.optimizer, "arena", None) is not None:
-            self.optimizer._flat_state()      # Adam's lazily created state must exist BEFORE the capture (a captured
-                                              # zero-fill would reset it on every replay)
-        # ... and so must the process-wide scratch the step's kernels share (split-K partials and tickets, the norm's block
-        # partials, the backward seed): created inside a capture they would live in that graph's private pool while later
-        # captures and eager calls keep using them
         dev = batch[0].device
-        nv.splitk_scratch(dev)
-        if hasattr(self.optimizer, "norm_scratch"):
-            self.optimizer.norm_scratch(dev)
-        if self._seed is None or self._seed.device != dev:
+        if self._seed is None or self._seed.device != dev:       # (the backward seed: resident, like the shared scratch)
             self._seed = torch.ones((), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize()
+        prepare_capture(dev, self.optimizer)
         if self.reducer is not None and self.reducer.active:
             drain_collective_watchdog()
         cap = _Captured()
@@ -563,10 +490,7 @@ class TrainStep:
             and hasattr(self.model, "encoder")
         if self.reducer is not None:
             self.reducer.detach()                       # bucket all-reduces are issued explicitly between the graphs
-        # ProcessGroupNCCL's watchdog thread polls the events of outstanding collectives (hipEventQuery); under the
-        # default "global" capture mode that call from ANOTHER thread aborts the process ("operation not permitted
-        # when stream is capturing").  With a process group alive, only this thread's unsafe calls are policed.
-        mode = dict(capture_error_mode="thread_local") if torch.distributed.is_initialized() else {}
+        mode = capture_kwargs()
         if self.accumulate is not None:
             # two captures from one pool: the micro-batch (no zero_grad, no update), and the update (norm, clip + Adam, close);
             # with data parallelism the collectives run eagerly between them (_close_window)
@@ -607,7 +531,7 @@ class TrainStep:
                           "between three graphs" % (type(failure).__name__, failure))
             # the failed capture may have stopped anywhere: collectives noted as fired, tail buffers handed out, the
             # encoder cut stored, weight gradients still deferred - the recapture starts from a clean slate
-            from .functional import _Deferred
+            from .functional import TailBuffers, _Deferred
             self.reducer._work, self.reducer._fired = [], [False] * len(self.reducer.buckets)
             self._cut = None
             _Deferred.pending.clear()
@@ -647,73 +571,6 @@ class TrainStep:
             cap.gnorm = self._clip_and_update(left)
         # capture only records; the step that triggered it is executed by the replay that follows
         return cap
-
-
-class _Bucket:
-    """Bucket mode: static staging buffers, device-length layouts and the captured step of one (B, feature) shape."""
-    __slots__ = ("x", "tok", "gt", "gt_flat", "layouts", "cap", "seen", "tails")
-
-    def __init__(self):
-        self.x = self.tok = self.gt = self.gt_flat = self.layouts = self.cap = self.tails = None
-        self.seen = 0
-
-
-def stage_bucket(who, model, buckets, bucket, bucket_rows, inputs, input_lengths, targets, target_lengths, ground_truth):
-    """The staging of one batch into a bucket, shared by the step drivers (TrainStep, evaluate.EvalStep): the batch is copied
-    into the bucket's static padded buffers, the lengths (packed capacities: the offsets too) are refreshed on the device, the
-    encoder's work lists follow the batch.  ``buckets``: the driver's dict of _Bucket by (B, feature, dtype, device,
-    capacity); a missing one is created here - buffers, Rows.bucket layouts, chain plans and work lists, all before any capture.
-    -> (the _Bucket, the batch to run: static tensors + this batch's lengths, whether the layouts are packed)."""
-    T_cap, L_cap = bucket
-    B, T, Fd = inputs.shape
-    L = targets.shape[1]
-    if T > T_cap or L > L_cap or ground_truth.shape[1] > L_cap:
-        raise ValueError("%s(bucket=%r): batch of %d frames / %d tokens does not fit" % (who, bucket, T, L))
-    caps = None                   # the first packed capacity the batch fits (None: the padded bucket)
-    if bucket_rows is not None:
-        n_in, n_tgt = int(input_lengths.sum()), int(target_lengths.sum())
-        caps = next((c for c in bucket_rows if n_in <= c[0] and n_tgt <= c[1]), None)
-    packed = caps is not None
-    key = (B, Fd, inputs.dtype, str(inputs.device), caps)
-    st = buckets.get(key)
-    if st is None:
-        from .functional import Rows
-        dev = inputs.device
-        st = _Bucket()
-        st.x = torch.zeros(B, T_cap, Fd, dtype=inputs.dtype, device=dev)
-        st.tok = torch.zeros(B, L_cap, dtype=targets.dtype, device=dev)
-        # (one spare element behind the padded ground truth: the target of the rows a packed bucket leaves unassigned;
-        # it stays 0 = ignore_index)
-        st.gt_flat = torch.zeros(B * L_cap + 1, dtype=ground_truth.dtype, device=dev)
-        st.gt = st.gt_flat[:B * L_cap].view(B, L_cap)
-        in_cap, tgt_cap = caps if packed else (None, None)
-        st.layouts = (Rows.bucket(B, T_cap, dev, rows=in_cap), Rows.bucket(B, L_cap, dev, rows=tgt_cap))
-        if hasattr(model, "prepare_layouts"):          # chain plans, work lists: before any capture
-            from .functional import attn_work
-            model.prepare_layouts(torch.full((B,), T_cap), torch.full((B,), L_cap), L_cap, dev)
-            ir, tr = st.layouts
-            dk, nh = getattr(model, "_d_k", 64), getattr(model, "_n_head", 0)
-            attn_work(ir, ir, False, dk, nh), attn_work(tr, tr, True, dk, nh), attn_work(tr, ir, False, dk, nh)
-            tr.scatter_index(L_cap)
-        buckets[key] = st
-    st.x[:, :T].copy_(inputs, non_blocking=True)
-    if T < T_cap:
-        st.x[:, T:].zero_()                                  # no frame of an earlier batch survives behind a length
-    st.tok.zero_()
-    st.tok[:, :L].copy_(targets, non_blocking=True)
-    st.gt.zero_()                                            # padding positions: ground truth 0 = ignore_index
-    st.gt[:, :ground_truth.shape[1]].copy_(ground_truth, non_blocking=True)
-    st.layouts[0].set_lengths(input_lengths)
-    st.layouts[1].set_lengths(target_lengths)
-    if hasattr(model, "prepare_layouts"):
-        # the encoder self-attention's work lists follow the batch (longest utterance first); the decoder's attentions
-        # are a handful of short workgroups either way
-        from .functional import refresh_attn_work
-        ir = st.layouts[0]
-        refresh_attn_work(ir, ir, False, getattr(model, "_d_k", 64), getattr(model, "_n_head", 0),
-                          input_lengths.tolist(), input_lengths.tolist())
-    batch = (st.x, input_lengths, st.tok, target_lengths, st.gt_flat if packed else st.gt)
-    return st, batch, packed
 
 
 def drain_collective_watchdog(limit_s: float = 5.0) -> str:
@@ -812,14 +669,14 @@ class JointTrainStep:
         self._seed = None
         self._side = None
         self.ce_spec = ce_spec(getattr(head, "att_criterion", None), model.tgt_word_proj.weight.shape[0])
-        self._ce_denom, self._ce_denom_host = None, None      # as TrainStep: B * l_max (norm "rows") or 1 ("sum") on the device
+        self._denom = LossDenom()             # B * l_max (norm "rows") or 1 ("sum") on the device; read back as self._ce_denom
         self.nll = None
         self._options_token, self._head_avg = None, None
         self._bind_options()
 
     def _bind_options(self):
         """Carry the optimizer's options over to the head's optimizer (see the class docstring)."""
-        self._options_token = TrainStep._options(self)
+        self._options_token = optimizer_options(self.optimizer, "JointTrainStep")
         self._head_avg = None
         opt, hopt = self.optimizer, self.head_optimizer
         if hopt is None or self._options_token is None:
@@ -832,14 +689,18 @@ class JointTrainStep:
         if getattr(opt, "_avg_opts", None) is not None:
             params = [q for g in hopt.param_groups for q in g["params"]]
             self._head_avg = (params, opt.register_averaged(params))
-            self._options_token = TrainStep._options(self)
+            self._options_token = optimizer_options(self.optimizer, "JointTrainStep")
 
     def _check_options(self):
-        if TrainStep._options(self) != self._options_token:
+        if optimizer_options(self.optimizer, "JointTrainStep") != self._options_token:
             if self._cap is not None:
                 raise RuntimeError("JointTrainStep: the optimizer's options changed after this step was captured (the graph "
                                    "holds the old launches): enable them before the first capture, or build a new step")
             self._bind_options()
+
+    @property
+    def _ce_denom(self):
+        return self._denom.tensor
 
     def _average_head(self):
         if self._head_avg is not None:
@@ -942,85 +803,69 @@ class JointTrainStep:
     def __call__(self, inputs, input_lengths, targets, target_lengths, ground_truth):
         """-> (joint loss, attention CE, CTC loss, clip norm): device tensors."""
         self._check_options()
-        t_max, l_max = int(input_lengths.max()), int(target_lengths.max())
         self.global_step += 1
-        batch = (inputs[:, :t_max], input_lengths, targets[:, :l_max], target_lengths, ground_truth[:, :l_max])
-        TrainStep._stage_denom(self, batch[4].shape[0], batch[4].shape[1], inputs.device)
-        sig = (inputs.data_ptr(), targets.data_ptr(), ground_truth.data_ptr(), tuple(inputs.shape), tuple(targets.shape),
-               input_lengths.cpu().numpy().tobytes(), target_lengths.cpu().numpy().tobytes())
+        batch = trim_batch(inputs, input_lengths, targets, target_lengths, ground_truth)
+        self._denom.stage(getattr(self.ce_spec, "norm", None), batch[4].shape[0], batch[4].shape[1], inputs.device)
+        sig = batch_signature(inputs, input_lengths, targets, target_lengths, ground_truth)
         if sig != self._sig:
             self._sig, self._seen, self._cap = sig, 0, None
-            self._layouts = self.model.prepare_layouts(batch[1], batch[3], l_max, inputs.device)
+            self._layouts = self.model.prepare_layouts(batch[1], batch[3], batch[4].shape[1], inputs.device)
             # the CTC labels are the ground truth of train.py:40 (label ids, PAD = blank = 0 past each length)
             self._plan = self.head.plan(batch[4], batch[3], batch[1], self._layouts[0])
             self._keep = batch
         plan, layouts = self._plan, self._layouts
         self.optimizer.update_learning_rate(self.global_step)
-        if self.ctc == "hip":
-            return self._call_hip(batch, plan, layouts)
-        main = torch.cuda.current_stream()
         if not self.use_graph or self._seen < self.graph_warmup:
             self._seen += 1
-            enc, lp = self._part_a1(batch, plan, layouts)
-            ctc, done = self._side_ctc(lp, plan)
-            att, enc_in = self._part_a2(batch, enc, layouts)
-            main.wait_event(done)
-            gnorm = self._part_b(enc, enc_in, lp, plan)
-            return self._joint(att, ctc), att, ctc, gnorm
+            return self._step(batch, plan, layouts)
         if self._cap is None:
-            self._before_capture(inputs.device)
-            torch.cuda.synchronize()
-            pool = torch.cuda.graph_pool_handle()
-            ga1, ga2, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            self._before_capture(inputs.device, plan)
             with no_gc_inside_capture():
-                with torch.cuda.graph(ga1, pool=pool):
-                    enc, lp = self._part_a1(batch, plan, layouts)
-                with torch.cuda.graph(ga2, pool=pool):
-                    att, enc_in = self._part_a2(batch, enc, layouts)
-                with torch.cuda.graph(gb, pool=pool):
-                    gnorm = self._part_b(enc, enc_in, lp, plan)
-            self._cap = (ga1, ga2, gb, att, lp, gnorm)
+                self._cap = self._capture(batch, plan, layouts)
+        if self.ctc == "hip":
+            graph, out = self._cap
+            graph.replay()
+            return out
         ga1, ga2, gb, att, lp, gnorm = self._cap
         ga1.replay()
         ctc, done = self._side_ctc(lp, plan)
         ga2.replay()
-        main.wait_event(done)
+        torch.cuda.current_stream().wait_event(done)
         gb.replay()
         return self._joint(att, ctc), att, ctc, gnorm
 
-    def _step_hip(self, batch, plan, layouts):
-        """The whole step as one sequence on the current stream (ctc="hip"): -> (joint loss, attention CE, CTC loss, clip norm)"""
+    def _step(self, batch, plan, layouts):
+        """The whole step as one sequence on the current stream - with ctc="torch", ctc_loss beside part A2 on the side stream:
+        the eager step, and what the one graph of ctc="hip" records.  -> (joint loss, attention CE, CTC loss, clip norm)"""
         enc, lp = self._part_a1(batch, plan, layouts)
-        ctc = self._ctc(lp, plan)
+        ctc, done = (self._ctc(lp, plan), None) if self.ctc == "hip" else self._side_ctc(lp, plan)
         att, enc_in = self._part_a2(batch, enc, layouts)
+        if done is not None:
+            torch.cuda.current_stream().wait_event(done)
         gnorm = self._part_b(enc, enc_in, lp, plan)
         return self._joint(att, ctc), att, ctc, gnorm
 
-    def _call_hip(self, batch, plan, layouts):
-        if not self.use_graph or self._seen < self.graph_warmup:
-            self._seen += 1
-            return self._step_hip(batch, plan, layouts)
-        if self._cap is None:
-            self._before_capture(batch[0].device)
-            plan.loss_workspace()                 # alpha / beta belong to the plan, not to the graph's pool
-            torch.cuda.synchronize()
+    def _capture(self, batch, plan, layouts):
+        """ctc="hip": the step as ONE graph.  ctc="torch": its three parts as three graphs from one pool - ctc_loss runs between
+        them at every replay (``__call__``), so the capture itself leaves it out.  Capture only records."""
+        if self.ctc == "hip":
             graph = torch.cuda.CUDAGraph()
-            with no_gc_inside_capture(), torch.cuda.graph(graph):
-                out = self._step_hip(batch, plan, layouts)
-            self._cap = (graph, out)
-        graph, out = self._cap
-        graph.replay()
-        return out
+            with torch.cuda.graph(graph):
+                out = self._step(batch, plan, layouts)
+            return graph, out
+        pool = torch.cuda.graph_pool_handle()
+        ga1, ga2, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(ga1, pool=pool):
+            enc, lp = self._part_a1(batch, plan, layouts)
+        with torch.cuda.graph(ga2, pool=pool):
+            att, enc_in = self._part_a2(batch, enc, layouts)
+        with torch.cuda.graph(gb, pool=pool):
+            gnorm = self._part_b(enc, enc_in, lp, plan)
+        return ga1, ga2, gb, att, lp, gnorm
 
-    def _before_capture(self, device):
-        """As TrainStep._capture: everything lazily created must exist BEFORE the capture - Adam's flat state (a captured zero-fill
-        would reset it on every replay), the process-wide scratch the step's kernels share (split-K partials and tickets, the
-        norm's block partials: inside a capture they would land in this graph's private pool), the seed."""
-        if hasattr(self.optimizer, "_flat_state") and getattr(self.optimizer, "arena", None) is not None:
-            self.optimizer._flat_state()
-        nv.splitk_scratch(device)
-        if hasattr(self.optimizer, "norm_scratch"):
-            self.optimizer.norm_scratch(device)
+    def _before_capture(self, device, plan):
+        """What must exist before the capture and is this driver's own - the seed, the head optimizer's state, the HIP CTC
+        loss's workspace - then stepdriver.prepare_capture."""
         if self._seed is None or self._seed.device != device:
             self._seed = torch.empty((), dtype=torch.float32, device=device)
         if self.head_optimizer is not None:
@@ -1032,6 +877,9 @@ class JointTrainStep:
                 raise ValueError("JointTrainStep(use_graph=True): head_optimizer has no state yet - run at least one eager "
                                  "step first (graph_warmup >= 1): state created inside the capture would be reset by "
                                  "every replay")
+        if self.ctc == "hip":
+            plan.loss_workspace()                 # alpha / beta belong to the plan, not to the graph's pool
+        prepare_capture(device, self.optimizer)
 
     @property
     def graphs(self):

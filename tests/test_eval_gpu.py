@@ -289,6 +289,56 @@ def test_bucket_graph_equals_eager_bit_for_bit(layout, kind):
     assert rp["tokens"] == tokens and abs(rp["nll"] - r["nll"]) <= STEP_LOSS_TOL * r["nll"]
 
 
+def test_train_and_eval_bucket_captures_interleaved():
+    """A TrainStep and an EvalStep on ONE model, both capturing a packed bucket, called alternately: each driver's warm-up,
+    its recording call and its capture fall between the other's (what they share is the process-wide TailBuffers.active of
+    stepdriver.bucket_step).  The model and the batches are those of tests/test_composition_cpu.py:run_bucket_mode, without
+    its over-long batch - all six fit the one packed capacity; so are the bounds of the train step against an eager twin.
+    Every eval call equals, bit for bit, a fresh eager EvalStep over the same bucket layouts on the same weights."""
+    import copy
+    import oracle as orc
+    import transformer.Models as M
+    import transformer.Utils as U
+    from st_amd.evaluate import EvalStep
+    from st_amd.functional import TailBuffers
+    from st_amd.trainer import TrainStep
+    from transformer.Optim import ScheduledOptim
+    t_cap, l_cap, rows = 96, 12, (340, 44)
+    torch.manual_seed(5)
+    cfg = U.AttrDict(dict(feature_dim=80, max_inputs_length=t_cap, max_target_length=l_cap, num_enc_layer=2, num_dec_layer=2,
+                          n_heads=4, d_k=64, d_v=64, d_model=256, d_inner_hid=512, dropout=0.0, vocab_size=30))
+    ma = M.Transformer(cfg)
+    U.init_parameters(ma)
+    mb = copy.deepcopy(ma)
+    ma, mb = ma.eval().cuda(), mb.eval().cuda()
+    kw = dict(bucket=(t_cap, l_cap), bucket_rows=rows)
+    sa = TrainStep(ma, ScheduledOptim(ma, 256, U.AttrDict(n_warmup_steps=50)), 30, 5.0, use_graph=True, graph_warmup=1, **kw)
+    sb = TrainStep(mb, ScheduledOptim(mb, 256, U.AttrDict(n_warmup_steps=50)), 30, 5.0, use_graph=False)
+    ev = EvalStep(ma, 30, use_graph=True, **kw)
+    seen = set()
+    for i in range(6):
+        b = orc.synthetic_batch(4, t_cap, l_cap, 80, 30, seed=20 + i, t_min=40, l_min=4)
+        assert int(b["in_len"].sum()) <= rows[0] and int(b["tgt_len"].sum()) <= rows[1]
+        seen.add((tuple(b["in_len"].tolist()), tuple(b["tgt_len"].tolist())))
+        T, L = int(b["in_len"].max()), int(b["tgt_len"].max())
+        batch = (b["x"][:, :T].cuda(), b["in_len"], b["tokens"][:, :L].cuda(), b["tgt_len"], b["gt"][:, :L].cuda())
+        la, ga = sa(*batch)
+        lb, gb = sb(*batch)
+        la, ga, lb, gb = float(la), float(ga), float(lb), float(gb)
+        print("batch %d: train loss %.7g (eager twin %.7g), norm %.7g (%.7g)" % (i, la, lb, ga, gb))
+        assert TailBuffers.active is None
+        assert abs(la - lb) <= (1e-5 if i == 0 else 5e-3) * abs(lb), (i, la, lb)
+        assert abs(ga - gb) <= (1e-4 if i == 0 else 3e-2) * abs(gb), (i, ga, gb)
+        got = ev(*batch).clone()
+        assert TailBuffers.active is None
+        want = EvalStep(ma, 30, use_graph=False, **kw)(*batch)
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), (i, got.tolist(), want.tolist())
+    assert len(seen) == 6, "the batches' lengths must not repeat"
+    for drv in (sa, ev):
+        assert len(drv._buckets) == 1 and next(iter(drv._buckets.values())).cap is not None
+    assert TailBuffers.active is None
+
+
 def _train_batches():
     """Single utterances of at most 30 frames and 6 tokens.  The training step adds its LayerNorm / bias column sums and the
     embedding gradient with fp32 atomics (include/st_hip.h: "accumulated atomically"), so with two or more workgroups per launch
