@@ -41,7 +41,7 @@ typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C:
  * ST_EPI_* values; comments, whitespace, parameter names and `const` do not count), computed by native.abi_fingerprint():
  *   change a declaration - importing st_amd.native fails - paste the number its message prints.
  * So it cannot be forgotten, and there is nothing in it to assert by value: no test may spell it out. */
-#define ST_ABI_VERSION 1664642158
+#define ST_ABI_VERSION 101750792
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -603,6 +603,30 @@ int st_ctc_loss_grad(st_stream_t stream, const float* lp, int B, int T, int C, c
 int st_ctc_align_ws_kib(int B, int T, int L);
 int st_ctc_align(st_stream_t stream, const float* lp, int B, int T, int C, const long long* classes, int L, const int* in_len,
                  const int* tgt_len, void* ws, long long ws_bytes, int* path, int* spans, float* score);
+
+/* CTC prefix beam search (csrc/st_ctc_beam.hip): per utterance the `beam` most probable label prefixes under the CTC head, each
+ * the sum over its alignments, with scores - one wave per utterance, one launch per batch, nothing read from host memory.
+ * ids i32 / lp f32 [R][K]: the K (1..16) best classes of every packed row's log-softmax, best first (what st_beam_pre_beam writes
+ * with n = R); lpb f32 [R]: the blank's log-probability of every row (blank is always a candidate, among the K best or not);
+ * off, len i32 [B]: utterance b owns rows off[b] .. off[b] + len[b] - 1 (rows outside are never read).  beam 1..16, L_cap 1..255.
+ * Recursion per frame t, C_t = the non-blank classes among the row's K: stay p (candidate number = slot): pb' = total(p) + lpb_t,
+ * pnb' = pnb(p) + x_t(last(p)) if last(p) in C_t; extension p.c, c in C_t, len(p) < L_cap (number beam + slot K + j):
+ * pnb' = (c == last(p) ? pb(p) : total(p)) + x_t(c); total = logaddexp(pb, pnb).  An extension that spells the labels of a beam
+ * entry ADDS into that entry (identity by label sequence, checked label by label - never by lineage or hash alone), log-sums in
+ * candidate order; the `beam` best totals are kept, lower candidate number on ties, a total of -inf never.  fp32 natural units
+ * relative to the frame's best total, the normaliser carried in fp64; fixed order, no atomics: launches are bit-equal.
+ * tokens i32 [B][beam][L_cap] (-1 past a length), lens i32 [B][beam], score f32 [B][beam] best first (normaliser + relative total,
+ * rounded once); slots past the live prefixes: score -inf, length 0, tokens -1; len[b] = 0: the empty prefix with score 0 in slot
+ * 0.  Every byte of the three outputs is written.
+ * trace (NULL: not written): 16-byte records {i32 prev_slot, i32 token (-1: same prefix), f32 pb_rel, f32 pnb_rel} of the beam AFTER
+ * frame t, [B][T_trace][beam] (a dead slot: -1, -1, -inf, -inf); trace_norm f64 [B][T_trace]: the normaliser after frame t (the sum
+ * of the frames' best totals).  Frames t >= len[b] and t >= T_trace are not written.
+ * st_ctc_beam_ws_kib: host query, no launch: -1 for an unsupported shape, else 0 - the label sequences of the beam live in LDS and
+ * no state grows with the frame count, so any len[b] is supported without a workspace. */
+int st_ctc_beam_ws_kib(int B, int T, int beam, int L_cap);
+int st_ctc_beam_search(st_stream_t stream, const int* ids, const float* lp, const float* lpb, const int* off, const int* len, int B,
+                       int K, int beam, int blank, int L_cap, int* tokens, int* lens, float* score, void* trace,
+                       double* trace_norm, int T_trace);
 
 /* Attention probabilities of ONE attention sublayer, materialised (reference transformer/Attention.py:89,96: the `attns`
  * MultiHeadAttention.forward returns; Models.py:53-54,107-109 collect them under return_attns): P (f32 [B, H, Lq, Lk],

@@ -1,0 +1,117 @@
+"""CTC prefix beam search on the device and the glue of two-pass decoding (CTC n-best, attention rescoring).
+
+``search_rows(head, enc_rows, in_rows, beam)`` runs the CTC head over the packed encoder rows (one ``st_gemm``), takes the
+``pre_beam`` best classes of every row's log-softmax (``st_beam_pre_beam``), reads the blank's log-probability off the same
+numbers (no further pass over the logits: the row's log-sum-exp is logit(best) - lp(best)) and searches all utterances with ONE
+``st_ctc_beam_search`` launch (csrc/st_ctc_beam.hip: one wave per utterance; prefixes are merged by their labels).  The decoder is
+never touched.  ``combine`` is the host side of ``Decode.decode_two_pass``: the joint score of every first-pass hypothesis from
+its CTC and its teacher-forced attention score, re-sorted."""
+import torch
+
+from . import ctc_decode
+from . import native as nv
+
+F32, I32, I64 = torch.float32, torch.int32, torch.int64
+MAX_V = 5120              # st_beam_pre_beam's vocabulary limit
+
+
+class NBest(object):
+    """Device tensors of one searched batch: ``tokens`` i32 [B, N, L_cap] (-1 past a length), ``lens`` i32 [B, N], ``score`` f32
+    [B, N] - log p_ctc of the label prefix summed over the alignments the search kept; best first, -inf where an utterance has
+    fewer than N live prefixes."""
+
+    __slots__ = ("tokens", "lens", "score")
+
+    def __init__(self, tokens, lens, score):
+        self.tokens, self.lens, self.score = tokens, lens, score
+
+    def lists(self):
+        """-> (labels[b][j]: the label list of hypothesis j of utterance b, scores: f32 [B, N] on the host).  One host read."""
+        B, N, L = self.tokens.shape
+        host = torch.cat([self.tokens.reshape(B, N * L).double(), self.lens.double(), self.score.double()], 1).cpu()
+        lens = host[:, N * L:N * L + N].long().tolist()
+        toks = host[:, :N * L].long().view(B, N, L).tolist()
+        return [[toks[b][j][:lens[b][j]] for j in range(N)] for b in range(B)], host[:, N * L + N:].float()
+
+
+def check_widths(V, beam, pre_beam=None, n_best=None):
+    """-> (beam, K, N) of a search over a vocabulary of V classes; ValueError on a bad combination."""
+    beam = int(beam)
+    K = beam if pre_beam is None else int(pre_beam)
+    N = beam if n_best is None else int(n_best)
+    if V > MAX_V:
+        raise ValueError("ctc_beam: vocabularies above %d classes are not supported (got %d)" % (MAX_V, V))
+    if not 1 <= beam <= nv.CTC_BEAM_MAX:
+        raise ValueError("ctc_beam: beam must lie in [1, %d], got %d" % (nv.CTC_BEAM_MAX, beam))
+    if not 1 <= K <= nv.CTC_BEAM_MAX:
+        raise ValueError("ctc_beam: pre_beam must lie in [1, %d], got %d" % (nv.CTC_BEAM_MAX, K))
+    if K > V:
+        raise ValueError("ctc_beam: pre_beam %d exceeds the vocabulary %d" % (K, V))
+    if not 1 <= N <= beam:
+        raise ValueError("ctc_beam: n_best must lie in [1, beam] = [1, %d], got %d" % (beam, N))
+    return beam, K, N
+
+
+def label_capacity(t_max, max_len=None):
+    """L_cap of a search: an utterance of T rows spells at most T labels; the kernel holds 255."""
+    cap = nv.CTC_LOSS_MAX_L if max_len is None else int(max_len)
+    if not 1 <= cap <= nv.CTC_LOSS_MAX_L:
+        raise ValueError("ctc_beam: max_len must lie in [1, %d], got %d" % (nv.CTC_LOSS_MAX_L, cap))
+    return max(1, min(cap, int(t_max)))
+
+
+@torch.no_grad()
+def search_logits(logits, V, in_rows, blank, beam, K, L_cap):
+    """The search over the head's logits f32 [R, >= V] -> NBest with N = beam."""
+    dev, R, B = logits.device, logits.shape[0], in_rows.B
+    ids = torch.empty(R, K, dtype=I32, device=dev)
+    lp = torch.empty(R, K, dtype=F32, device=dev)
+    nv.beam_pre_beam(logits, V, ids, lp)
+    best = logits.gather(1, ids[:, :1].to(I64)).squeeze(1)
+    lpb = (logits[:, int(blank)] - (best - lp[:, 0])).contiguous()
+    tokens = torch.empty(B, beam, L_cap, dtype=I32, device=dev)
+    lens = torch.empty(B, beam, dtype=I32, device=dev)
+    score = torch.empty(B, beam, dtype=F32, device=dev)
+    nv.ctc_beam_search(ids, lp, lpb, in_rows.off, in_rows.len, blank, tokens, lens, score)
+    return NBest(tokens, lens, score)
+
+
+@torch.no_grad()
+def search_rows(head, enc, in_rows, beam, pre_beam=None, n_best=None, max_len=None):
+    """head: the ``transformer.Loss.CTCAttentionLoss`` of a joint model; enc bf16 [sum(len), d] + in_rows: the packed encoder
+    output (``Encoder.forward_rows``) -> NBest of the ``n_best`` (default ``beam``) best label prefixes per utterance.
+    ``pre_beam`` (default ``beam``): classes considered per row; ``max_len``: label capacity (default min(255, longest utterance))."""
+    V = head.ctc_proj.weight.shape[0]
+    beam, K, N = check_widths(V, beam, pre_beam, n_best)
+    L_cap = label_capacity(in_rows.max_len, max_len)
+    out = search_logits(ctc_decode.head_logits(head, enc), V, in_rows, int(head.blank), beam, K, L_cap)
+    if N < beam:
+        out = NBest(out.tokens[:, :N].contiguous(), out.lens[:, :N].contiguous(), out.score[:, :N].contiguous())
+    return out
+
+
+def combine(hyps, ctc_scores, att_scores, weight, n_best, eos):
+    """Second-pass ranking on the host.  hyps[b][j]: label lists (no EOS); ctc_scores, att_scores: [B, N] - the first pass' log
+    p_ctc(h) and the teacher-forced log p_att(h . EOS); a missing hypothesis has -inf in either.  Final score
+    (1 - w) att + w ctc (w = 0: the attention score alone), sorted best first (the first pass' order on ties), the ``n_best`` kept
+    -> (all_hyp with EOS closing every list, scores f32 [B, n_best]); a slot without a hypothesis: ([], -inf)."""
+    w = float(weight)
+    if not 0.0 <= w < 1.0:
+        raise ValueError("decode_two_pass: ctc_weight must lie in [0, 1), got %r" % w)
+    ctc = torch.as_tensor(ctc_scores).double().cpu()
+    att = torch.as_tensor(att_scores).double().cpu()
+    B, N = ctc.shape
+    if tuple(att.shape) != (B, N) or len(hyps) != B or not 1 <= int(n_best) <= N:
+        raise ValueError("decode_two_pass: %d x %d first-pass scores, second-pass %s, %d lists, n_best %d"
+                         % (B, N, tuple(att.shape), len(hyps), n_best))
+    ninf = torch.full_like(ctc, float("-inf"))
+    missing = torch.isinf(ctc) | torch.isinf(att) | torch.isnan(att)
+    final = torch.where(missing, ninf, (1.0 - w) * att + (w * ctc if w > 0.0 else 0.0))
+    order = torch.sort(final, dim=1, descending=True, stable=True)[1][:, :int(n_best)]
+    all_hyp = []
+    for b in range(B):
+        row = []
+        for j in order[b].tolist():
+            row.append([] if bool(missing[b, j]) else [int(k) for k in hyps[b][j]] + [int(eos)])
+        all_hyp.append(row)
+    return all_hyp, final.gather(1, order).float()

@@ -1126,6 +1126,76 @@ def ctc_align(lp, classes, in_len, tgt_len, ws, path, spans, score):
     return path, spans, score
 
 
+# ---- CTC prefix beam search (csrc/st_ctc_beam.hip) ---------------------------------------------------------------------------------
+CTC_BEAM_MAX = 16         # beam slots and classes per row of st_ctc_beam_search
+TRACE_REC_BYTES = 16      # {i32 prev_slot, i32 token, f32 pb_rel, f32 pnb_rel}
+
+
+def _ctc_beam_range(who, beam, L_cap, K=1):
+    if not (1 <= int(beam) <= CTC_BEAM_MAX and 1 <= int(K) <= CTC_BEAM_MAX):
+        raise ValueError("%s: beam and K must lie in [1, %d], got beam = %d, K = %d" % (who, CTC_BEAM_MAX, beam, K))
+    if not 1 <= int(L_cap) <= CTC_LOSS_MAX_L:
+        raise ValueError("%s: the label capacity must lie in [1, %d], got L_cap = %d" % (who, CTC_LOSS_MAX_L, L_cap))
+
+
+def ctc_beam_ws_bytes(B, T_max, beam, L_cap) -> int:
+    """Bytes of workspace st_ctc_beam_search wants (a host-only query: no launch, no GPU).  0 for every supported shape - the
+    beam's label sequences live in LDS and nothing grows with the frame count; ValueError for an unsupported one."""
+    if min(int(B), int(T_max)) < 0:
+        raise ValueError("ctc_beam: negative B or T_max")
+    _ctc_beam_range("ctc_beam", beam, L_cap)
+    kib = int(load()._cdll.st_ctc_beam_ws_kib(int(B), int(T_max), int(beam), int(L_cap)))
+    if kib < 0:
+        raise ValueError("st_ctc_beam_ws_kib: unsupported shape B = %d, T = %d, beam = %d, L_cap = %d" % (B, T_max, beam, L_cap))
+    return kib * 1024
+
+
+def ctc_beam_search(ids, lp, lpb, off, length, blank, tokens, lens, score, trace=None, trace_norm=None):
+    """CTC prefix beam search of B utterances in one launch - see st_ctc_beam_search.  ids i32 / lp f32 [R, K] (st_beam_pre_beam
+    over the CTC head's logits), lpb f32 [R], off / length i32 [B] (device: capturable) -> tokens i32 [B, beam, L_cap] (-1 past a
+    length), lens i32 [B, beam], score f32 [B, beam] (best first; -inf in the slots past the live prefixes).  ``trace`` u8
+    [B, T_trace, beam, 16] + ``trace_norm`` f64 [B, T_trace]: the per-frame records of the beam (both or neither)."""
+    who = "ctc_beam_search"
+    if ids.dim() != 2 or ids.dtype != I32 or not ids.is_contiguous():
+        raise ValueError("%s: ids must be a contiguous i32 [R, K] tensor, got %s %s" % (who, ids.dtype, tuple(ids.shape)))
+    R, K = ids.shape
+    if tokens.dim() != 3 or tokens.dtype != I32 or not tokens.is_contiguous():
+        raise ValueError("%s: tokens must be a contiguous i32 [B, beam, L_cap] tensor, got %s %s" % (who, tokens.dtype, tuple(tokens.shape)))
+    B, beam, L_cap = tokens.shape
+    _ctc_beam_range(who, beam, L_cap, K)
+    if off.dim() != 1 or off.shape[0] != B:
+        raise ValueError("%s: off must hold one row offset per utterance (B = %d), got %s" % (who, B, tuple(off.shape)))
+    for name, t, dtype, shape in (("lp", lp, F32, (R, K)), ("lpb", lpb, F32, (R,)), ("off", off, I32, (B,)), ("length", length, I32, (B,)),
+                                  ("lens", lens, I32, (B, beam)), ("score", score, F32, (B, beam))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s %s tensor, got %s %s" % (who, name, dtype, list(shape), t.dtype, tuple(t.shape)))
+    if (trace is None) != (trace_norm is None):
+        raise ValueError("%s: trace and trace_norm go together" % who)
+    T_trace = 0
+    if trace is not None:
+        if trace.dim() != 4 or trace.dtype != torch.uint8 or not trace.is_contiguous() or trace.shape[0] != B or trace.shape[1] < 1 \
+                or tuple(trace.shape[2:]) != (beam, TRACE_REC_BYTES):
+            raise ValueError("%s: trace must be a contiguous u8 [B, T_trace >= 1, beam, %d] tensor, got %s %s"
+                             % (who, TRACE_REC_BYTES, trace.dtype, tuple(trace.shape)))
+        T_trace = trace.shape[1]
+        if trace_norm.dtype != torch.float64 or tuple(trace_norm.shape) != (B, T_trace) or not trace_norm.is_contiguous():
+            raise ValueError("%s: trace_norm must be a contiguous f64 [B, T_trace] tensor, got %s %s"
+                             % (who, trace_norm.dtype, tuple(trace_norm.shape)))
+    if not 0 <= int(blank):
+        raise ValueError("%s: blank must be a class id, got %d" % (who, blank))
+    for name, t in (("ids", ids), ("lp", lp), ("lpb", lpb), ("off", off), ("length", length), ("tokens", tokens), ("lens", lens),
+                    ("score", score), ("trace", trace), ("trace_norm", trace_norm)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("%s: %s must live on the GPU: the HIP path has no CPU fallback" % (who, name))
+    if trace is not None and trace.data_ptr() % 16:
+        raise ValueError("%s: trace must be 16-byte aligned" % who)
+    _tag("ctc_beam_search", B, R, K, beam, io=(ids, lp, lpb, tokens))
+    _check(load().st_ctc_beam_search(_stream(), ids.data_ptr(), lp.data_ptr(), lpb.data_ptr(), off.data_ptr(), length.data_ptr(), B, K,
+                                     beam, int(blank), L_cap, tokens.data_ptr(), lens.data_ptr(), score.data_ptr(), _p(trace),
+                                     _p(trace_norm), T_trace), "st_ctc_beam_search")
+    return tokens, lens, score
+
+
 def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False, out=None):
     """The attention probabilities of one sublayer, materialised: f32 [B, n_head, Lq, Lk] (zeros at masked keys and in the
     rows of padding positions).  Q, K: bf16 row matrices (column slices of the q | k | v projection are fine).  out: the

@@ -176,15 +176,19 @@ class Decode(object):
         cur.wait_stream(self._side)
         return out
 
-    def _init_state(self, src_batch, beam, arena, search=True, ctc=None):
+    def _init_state(self, src_batch, beam, arena, search=True, ctc=None, encoded=None):
         """Encoder pass + the device state of a search over ``beam`` hypotheses per utterance (call inside ``arena.scope()``).
-        ``ctc`` = (pre-beam width K, weight): also the CTC side of a joint search (st_amd.ctc_decode.CtcSearch)."""
+        ``ctc`` = (pre-beam width K, weight): also the CTC side of a joint search (st_amd.ctc_decode.CtcSearch).
+        ``encoded`` = (enc, in_rows): the encoder output of this batch, already computed in this scope (None: run the encoder)."""
         inputs, in_len = src_batch
         model, dev = self.model, self.device
-        inputs = inputs.to(dev)
         B = inputs.shape[0]
-        t_max = int(in_len.max())
-        enc, in_rows = model.encoder.forward_rows(inputs[:, :t_max], in_len)        # packed [sum T, d]
+        if encoded is None:
+            inputs = inputs.to(dev)
+            t_max = int(in_len.max())
+            enc, in_rows = model.encoder.forward_rows(inputs[:, :t_max], in_len)    # packed [sum T, d]
+        else:
+            enc, in_rows = encoded
         dec = model.decoder
         d, S, n = dec.d_model, self.max_steps, B * beam
         if S > dec.position_enc.pe.shape[1]:
@@ -308,6 +312,105 @@ class Decode(object):
             out.append(labels)
             o += int(T)
         return out
+
+    def _encode(self, src_batch):
+        """-> (enc bf16 [sum T, d], in_rows) of the batch (call inside ``arena.scope()``)."""
+        inputs, in_len = src_batch
+        return self.model.encoder.forward_rows(inputs.to(self.device)[:, :int(in_len.max())], in_len)
+
+    def _ctc_widths(self, who, beam, n_best):
+        from st_amd import ctc_beam
+        if self.ctc_head is None:
+            raise ValueError("%s: needs the CTC head (Decode(..., ctc_head=...))" % who)
+        beam = int(self.opt.beam_size if beam is None else beam)
+        n_best = int(self.opt.n_best if n_best is None else n_best)
+        return ctc_beam.check_widths(self.model.vocab_size, beam, getattr(self.opt, "ctc_beam_pre_beam", None), n_best)
+
+    @torch.no_grad()
+    def ctc_beam(self, src_batch, beam=None, n_best=None):
+        """CTC prefix beam search with the CTC head (st_amd.ctc_beam: the encoder-only first pass): per utterance the ``n_best``
+        most probable label lists under the head, each summed over its alignments.  -> (all_hyp, all_scores) shaped as
+        decode_batch's: all_hyp[b] = n_best label lists WITHOUT EOS (as ctc_greedy), all_scores[b] = their log-probabilities
+        (tensor[n_best], best first; an utterance with fewer live prefixes: [] with -inf).  ``beam`` defaults to
+        ``opt.beam_size``, ``n_best`` to ``opt.n_best``; ``opt.ctc_beam_pre_beam`` (default ``beam``): classes considered per row.
+        One encoder pass, one st_ctc_beam_search launch and one host read per batch; the decoder does not run."""
+        from st_amd import ctc_beam
+        beam, K, N = self._ctc_widths("ctc_beam", beam, n_best)
+        with arena_of(self.model).scope():
+            enc, in_rows = self._encode(src_batch)
+            hyps, scores = ctc_beam.search_rows(self.ctc_head, enc, in_rows, beam, K, N).lists()
+        return hyps, list(scores.to(self.device).unbind(0))
+
+    def _nbest_rows(self, src_batch, nbest, arena, encoded=None):
+        """Teacher-forced log p_att(h . EOS) of nbest[b][j] -> f64 [B, N] on the device (call inside ``arena.scope()``): the decode
+        path with the search off, N rows per utterance - one encoder pass (or none: ``encoded``), one cross K|V projection and one
+        decoder step per position for ALL rows."""
+        B, V, dev = src_batch[0].shape[0], self.model.vocab_size, self.device
+        if len(nbest) != B:
+            raise ValueError("score_nbest: %d n-best lists for %d utterances" % (len(nbest), B))
+        N = max(1, max(len(hs) for hs in nbest))
+        steps = 1 + max([len(h) for hs in nbest for h in hs] or [0])
+        if steps > self.max_steps:
+            raise ValueError("score_nbest: a hypothesis of %d labels plus EOS exceeds max_steps = %d" % (steps - 1, self.max_steps))
+        fed = torch.full((steps, B * N), Constants.PAD, dtype=torch.long)
+        live = torch.zeros(steps, B * N, dtype=torch.float64)
+        have = torch.zeros(B * N, dtype=torch.bool)
+        for b, hs in enumerate(nbest):
+            for j, h in enumerate(hs):
+                if h is None:
+                    continue
+                h = [int(k) for k in h]
+                if any(k < 0 or k >= V for k in h):
+                    raise ValueError("score_nbest: utterance %d has a token outside the vocabulary [0, %d)" % (b, V))
+                fed[:len(h) + 1, b * N + j] = torch.tensor(h + [Constants.EOS], dtype=torch.long)
+                live[:len(h) + 1, b * N + j] = 1.0
+                have[b * N + j] = True
+        fed, live, have = fed.to(dev), live.to(dev), have.to(dev)
+        st = self._init_state(src_batch, N, arena, search=False, encoded=encoded)
+        total = torch.zeros(B * N, dtype=torch.float64, device=dev)
+        for t in range(steps):
+            lp = torch.log_softmax(self._step(st)[:, :V].double(), -1)
+            total += lp.gather(1, fed[t].unsqueeze(1)).squeeze(1) * live[t]
+            st.tokens.copy_(fed[t])                     # rows stay where they are: no back-pointers, no cache moves
+            st.step.add_(1)
+            if st.need_c_len:
+                st.c_len.add_(1)
+        return torch.where(have, total, torch.full_like(total, float("-inf"))).view(B, N)
+
+    @torch.no_grad()
+    def score_nbest(self, src_batch, nbest):
+        """Teacher-forced attention scores of an n-best list: nbest[b] = up to N label lists WITHOUT EOS (``ctc_beam``'s) ->
+        f32 [B, N], log p_att(h . EOS) of each, -inf for a missing one (a shorter nbest[b], or None in it).  The decode path of
+        ``score_hypotheses`` with N rows per utterance in ONE pass: the encoder, the cross-attention K|V projections and every
+        decoder step are shared by all B x N hypotheses; no top-k, no cache lineage, no pre-beam."""
+        arena = arena_of(self.model)
+        with arena.scope():
+            return self._nbest_rows(src_batch, nbest, arena).float()
+
+    @torch.no_grad()
+    def decode_two_pass(self, src_batch, ctc_weight=None, beam=None, n_best=None):
+        """Two-pass decoding ("attention rescoring"): the encoder once, a CTC prefix beam search for ``beam`` hypotheses
+        (``ctc_beam``), their teacher-forced attention scores in one batched pass (``score_nbest``), and the joint score
+        (1 - w) log p_att(h . EOS) + w log p_ctc(h) - w = ``ctc_weight``, default ``opt.ctc_weight`` - re-sorted, the ``n_best``
+        kept.  -> (all_hyp, all_scores) as decode_batch returns them, EOS closing every list (``align`` takes them as they are).
+        Hypotheses are capped at max_steps - 1 labels."""
+        from st_amd import ctc_beam
+        w = float((getattr(self.opt, "ctc_weight", None) or 0.0) if ctc_weight is None else ctc_weight)
+        if not 0.0 <= w < 1.0:
+            raise ValueError("decode_two_pass: ctc_weight must lie in [0, 1), got %r" % w)
+        beam, K, N = self._ctc_widths("decode_two_pass", beam, n_best)
+        if self.max_steps < 2:
+            raise ValueError("decode_two_pass: max_steps must allow a label and EOS")
+        arena = arena_of(self.model)
+        with arena.scope():
+            enc, in_rows = self._encode(src_batch)
+            first = ctc_beam.search_rows(self.ctc_head, enc, in_rows, beam, K, None, max_len=min(255, self.max_steps - 1))
+            hyps, ctc_scores = first.lists()
+            fin = torch.isfinite(ctc_scores)
+            nbest = [[h if bool(fin[b, j]) else None for j, h in enumerate(hs)] for b, hs in enumerate(hyps)]
+            att = self._nbest_rows(src_batch, nbest, arena, encoded=(enc, in_rows)).cpu()
+        all_hyp, scores = ctc_beam.combine(hyps, ctc_scores, att, w, N, Constants.EOS)
+        return all_hyp, list(scores.to(self.device).unbind(0))
 
     @torch.no_grad()
     def align(self, src_batch, hyps, strip_eos=True):
