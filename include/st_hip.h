@@ -41,7 +41,7 @@ typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C:
  * ST_EPI_* values; comments, whitespace, parameter names and `const` do not count), computed by native.abi_fingerprint():
  *   change a declaration - importing st_amd.native fails - paste the number its message prints.
  * So it cannot be forgotten, and there is nothing in it to assert by value: no test may spell it out. */
-#define ST_ABI_VERSION 101750792
+#define ST_ABI_VERSION 2011967259
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -627,6 +627,37 @@ int st_ctc_beam_ws_kib(int B, int T, int beam, int L_cap);
 int st_ctc_beam_search(st_stream_t stream, const int* ids, const float* lp, const float* lpb, const int* off, const int* len, int B,
                        int K, int beam, int blank, int L_cap, int* tokens, int* lens, float* score, void* trace,
                        double* trace_norm, int T_trace);
+
+/* Back-off n-gram language model for shallow fusion (csrc/st_ngram.hip; st_amd/ngram.py builds the arrays).  The model is a trie
+ * keyed in REVERSE - the node of the n-gram (w_1 .. w_m) is reached by w_m, w_{m-1}, .., w_1 - over token ids [0, V), V <= 5120,
+ * order N in 2..5: node v < V is the unigram of token v (logp[v] = +inf: no unigram), the children of a node are the consecutive
+ * nodes child_lo[node] .. child_lo[node + 1] - 1 sorted by tok; child_lo i32 [nodes + 1], tok i32 / logp f32 / bo f32 [nodes],
+ * natural log, suffix-closed (an n-gram's suffix without its oldest token is stored too).  Score of candidate c after the history
+ * h_k .. h_1 (h_1 most recent; the history ends at the first id outside [0, V), k <= N - 1): m = the depth the walk c, h_1, h_2, ..
+ * reaches and logp_m its value (no unigram: oov_logp, m = 1); bo_j = the back-off of the node reached by h_1 .. h_j (0 from the
+ * first missing child on); score = logp_m + bo_m + .. + bo_k in fp32, in that order, additions only.  Device memory only is read:
+ * every entry can be captured into a graph.
+ *
+ * st_ngram_score: one wave per hypothesis row i < n = B * beam, lane j = candidate cand[i][j] (i32 [n][K], K <= 64); hist i32
+ * [n][N - 1] oldest first, -1 = no token.  lm_out (NULL: not written) f32 [n][K] = the raw score; lp (NULL: not updated) f32
+ * [n][K]: lp += scale * lm + bias (scale >= 0; with scale = 0 only the bias is added; -inf stays -inf, no NaN).  A candidate outside
+ * [0, V) scores -inf.  A row whose most recent token is `eos` is frozen: raw 0, lp untouched.  done: NULL or u8 [B] - the rows of a
+ * done utterance are skipped, nothing written.
+ *
+ * st_ngram_advance: hist[i] <- shift(hist[parent[i]]) . tokens[i], in place, one workgroup per utterance (every parent value is
+ * read before any is written); parent / tokens: the i64 [n] vectors `order` / `tokens` of st_beam_advance_joint (global rows of
+ * the same utterance).  A frozen parent (most recent token eos) passes its history on unchanged; done (NULL or u8 [B]): skipped.
+ * beam * (N - 1) <= 256.
+ *
+ * st_ngram_score_seq: teacher-forced: tokens i32 [M][L_cap], lens i32 [M] -> out f32 [M][L_cap] = log p(tokens[m][t] | bos,
+ * tokens[m][:t]) for t < lens[m], 0 elsewhere; one thread per (list, position), the arithmetic of st_ngram_score. */
+int st_ngram_score(st_stream_t stream, const int* child_lo, const int* tok, const float* logp, const float* bo, int nodes, int V,
+                   int order, float oov_logp, const int* hist, const int* cand, int n, int K, int beam, const unsigned char* done,
+                   int eos, float scale, float bias, float* lm_out, float* lp);
+int st_ngram_advance(st_stream_t stream, int* hist, int order, const long long* parent, const long long* tokens,
+                     const unsigned char* done, int eos, int B, int beam);
+int st_ngram_score_seq(st_stream_t stream, const int* child_lo, const int* tok, const float* logp, const float* bo, int nodes, int V,
+                       int order, float oov_logp, const int* tokens, const int* lens, int M, int L_cap, int bos, float* out);
 
 /* Attention probabilities of ONE attention sublayer, materialised (reference transformer/Attention.py:89,96: the `attns`
  * MultiHeadAttention.forward returns; Models.py:53-54,107-109 collect them under return_attns): P (f32 [B, H, Lq, Lk],

@@ -90,11 +90,12 @@ def search_rows(head, enc, in_rows, beam, pre_beam=None, n_best=None, max_len=No
     return out
 
 
-def combine(hyps, ctc_scores, att_scores, weight, n_best, eos):
+def combine(hyps, ctc_scores, att_scores, weight, n_best, eos, extra=None):
     """Second-pass ranking on the host.  hyps[b][j]: label lists (no EOS); ctc_scores, att_scores: [B, N] - the first pass' log
     p_ctc(h) and the teacher-forced log p_att(h . EOS); a missing hypothesis has -inf in either.  Final score
     (1 - w) att + w ctc (w = 0: the attention score alone), sorted best first (the first pass' order on ties), the ``n_best`` kept
-    -> (all_hyp with EOS closing every list, scores f32 [B, n_best]); a slot without a hypothesis: ([], -inf)."""
+    -> (all_hyp with EOS closing every list, scores f32 [B, n_best]); a slot without a hypothesis: ([], -inf).  ``extra``: None, or
+    [B, N] added to the final score of every present hypothesis (the language-model term of shallow fusion; -inf there vetoes)."""
     w = float(weight)
     if not 0.0 <= w < 1.0:
         raise ValueError("decode_two_pass: ctc_weight must lie in [0, 1), got %r" % w)
@@ -106,7 +107,13 @@ def combine(hyps, ctc_scores, att_scores, weight, n_best, eos):
                          % (B, N, tuple(att.shape), len(hyps), n_best))
     ninf = torch.full_like(ctc, float("-inf"))
     missing = torch.isinf(ctc) | torch.isinf(att) | torch.isnan(att)
-    final = torch.where(missing, ninf, (1.0 - w) * att + (w * ctc if w > 0.0 else 0.0))
+    final = (1.0 - w) * att + (w * ctc if w > 0.0 else 0.0)
+    if extra is not None:
+        extra = torch.as_tensor(extra).double().cpu()
+        if tuple(extra.shape) != (B, N):
+            raise ValueError("decode_two_pass: the extra term is %s for %d x %d hypotheses" % (tuple(extra.shape), B, N))
+        final = final + torch.where(missing, torch.zeros_like(extra), extra)
+    final = torch.where(missing, ninf, final)
     order = torch.sort(final, dim=1, descending=True, stable=True)[1][:, :int(n_best)]
     all_hyp = []
     for b in range(B):

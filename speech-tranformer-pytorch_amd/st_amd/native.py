@@ -1196,6 +1196,80 @@ def ctc_beam_search(ids, lp, lpb, off, length, blank, tokens, lens, score, trace
     return tokens, lens, score
 
 
+# ---- n-gram language model (csrc/st_ngram.hip; st_amd/ngram.py) ----------------------------------------------------------------------
+NGRAM_MAX_ORDER, NGRAM_MAX_V = 5, 5120
+
+
+def _ngram_trie(trie, who):
+    """The five leading arguments of the st_ngram_* entries from a st_amd.ngram.DeviceTrie: (child_lo, tok, logp, bo, nodes)."""
+    V, N, nodes = int(trie.V), int(trie.order), int(trie.nodes)
+    if not (2 <= N <= NGRAM_MAX_ORDER and 1 <= V <= NGRAM_MAX_V and nodes >= V):
+        raise ValueError("%s: order %d / vocabulary %d / %d nodes outside order 2..%d, V <= %d, nodes >= V"
+                         % (who, N, V, nodes, NGRAM_MAX_ORDER, NGRAM_MAX_V))
+    return (_dev(trie.child_lo, I32, (nodes + 1,), who + ": child_lo"), _dev(trie.tok, I32, (nodes,), who + ": tok"),
+            _dev(trie.logp, F32, (nodes,), who + ": logp"), _dev(trie.bo, F32, (nodes,), who + ": bo"), nodes)
+
+
+def ngram_score(trie, hist, cand, done, eos, scale=1.0, bias=0.0, lm_out=None, lp=None):
+    """Language-model scores of every hypothesis's K candidates - see st_ngram_score.  hist i32 [n, order - 1] (oldest first, -1 =
+    no token), cand i32 [n, K], done bool [B] or None (n = B x beam), lm_out f32 [n, K] or None (the raw scores), lp f32 [n, K] or
+    None (updated in place: lp += scale lm + bias)."""
+    who = "ngram_score"
+    if cand.dim() != 2 or not 1 <= cand.shape[1] <= 64:
+        raise ValueError("%s: cand must be an i32 [n, K <= 64] tensor, got %s" % (who, tuple(cand.shape)))
+    args = _ngram_trie(trie, who)
+    n, K = cand.shape
+    _dev(cand, I32, (n, K), who + ": cand"), _dev(hist, I32, (n, trie.order - 1), who + ": hist")
+    beam = n
+    if done is not None:
+        B = done.numel()
+        if B <= 0 or n % B:
+            raise ValueError("%s: %d rows do not divide into the %d utterances of done" % (who, n, B))
+        _dev(done, torch.bool, (B,), who + ": done")
+        beam = n // B
+    if lm_out is not None:
+        _dev(lm_out, F32, (n, K), who + ": lm_out")
+    if lp is not None:
+        _dev(lp, F32, (n, K), who + ": lp")
+    if not float(scale) >= 0.0 or float(bias) != float(bias):
+        raise ValueError("%s: scale must be >= 0 and bias a number, got %r, %r" % (who, scale, bias))
+    _tag("ngram_score", n, K, trie.order)
+    _check(load().st_ngram_score(_stream(), *args, int(trie.V), int(trie.order), float(trie.oov_logp), hist.data_ptr(), cand.data_ptr(),
+                                 n, K, max(beam, 1), _p(done), int(eos), float(scale), float(bias), _p(lm_out), _p(lp)), "st_ngram_score")
+
+
+def ngram_advance(hist, order, tokens, done, eos, beam):
+    """The histories of the hypotheses a beam step chose, in place: hist[i] <- shift(hist[order[i]]) . tokens[i] - see
+    st_ngram_advance.  hist i32 [n, N - 1]; order / tokens i64 [n] (st_beam_advance_joint's); done bool [B] or None."""
+    who = "ngram_advance"
+    if hist.dim() != 2 or not 1 <= hist.shape[1] <= NGRAM_MAX_ORDER - 1:
+        raise ValueError("%s: hist must be an i32 [n, order - 1] tensor with order in 2..%d, got %s" % (who, NGRAM_MAX_ORDER, tuple(hist.shape)))
+    n, H = hist.shape
+    beam = int(beam)
+    if beam <= 0 or n % beam or beam * H > 256:
+        raise ValueError("%s: %d rows, beam %d, %d history tokens: beam must divide the rows and beam x tokens <= 256" % (who, n, beam, H))
+    _dev(hist, I32, (n, H), who + ": hist"), _dev(order, I64, (n,), who + ": order"), _dev(tokens, I64, (n,), who + ": tokens")
+    if done is not None:
+        _dev(done, torch.bool, (n // beam,), who + ": done")
+    _check(load().st_ngram_advance(_stream(), hist.data_ptr(), H + 1, order.data_ptr(), tokens.data_ptr(), _p(done), int(eos), n // beam,
+                                   beam), "st_ngram_advance")
+
+
+def ngram_score_seq(trie, tokens, lens, bos, out):
+    """Teacher-forced language-model scores: tokens i32 [M, L_cap], lens i32 [M] -> out f32 [M, L_cap] = log p(tokens[m][t] | bos,
+    tokens[m][:t]) for t < lens[m], 0 elsewhere - see st_ngram_score_seq."""
+    who = "ngram_score_seq"
+    args = _ngram_trie(trie, who)
+    if tokens.dim() != 2:
+        raise ValueError("%s: tokens must be an i32 [M, L_cap] tensor, got %s" % (who, tuple(tokens.shape)))
+    M, L = tokens.shape
+    _dev(tokens, I32, (M, L), who + ": tokens"), _dev(lens, I32, (M,), who + ": lens"), _dev(out, F32, (M, L), who + ": out")
+    _tag("ngram_score_seq", M, L, trie.order)
+    _check(load().st_ngram_score_seq(_stream(), *args, int(trie.V), int(trie.order), float(trie.oov_logp), tokens.data_ptr(),
+                                     lens.data_ptr(), M, L, int(bos), out.data_ptr()), "st_ngram_score_seq")
+    return out
+
+
 def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False, out=None):
     """The attention probabilities of one sublayer, materialised: f32 [B, n_head, Lq, Lk] (zeros at masked keys and in the
     rows of padding positions).  Q, K: bf16 row matrices (column slices of the q | k | v projection are fine).  out: the

@@ -28,6 +28,7 @@ import transformer.Constants as Constants
 from st_amd import ctc_decode
 from st_amd import functional as F_
 from st_amd import native as nv
+from st_amd import ngram
 from st_amd.arena import arena_of
 from transformer.Beam import Beam  # noqa: F401  (re-exported: the reference's Decode module exposes it)
 
@@ -38,18 +39,29 @@ LN_EPS = 1e-6
 class Decode(object):
     ''' Beam search over a trained Transformer. '''
 
-    def __init__(self, opt, device, model=None, ctc_head=None):
-        """opt: attribute-style (beam_size, n_best, [max_steps=100], [use_graph], [ctc_weight=0.0], [ctc_pre_beam]); model: a
+    def __init__(self, opt, device, model=None, ctc_head=None, lm=None):
+        """opt: attribute-style (beam_size, n_best, [max_steps=100], [use_graph], [ctc_weight=0.0], [ctc_pre_beam], [lm_weight=0.0],
+        [lm_length_bonus=0.0]); model: a
         transformer.Models.Transformer on ``device`` (the reference loads a checkpoint here with an API that no longer exists).
         ``ctc_head``: the ``transformer.Loss.CTCAttentionLoss`` a joint model was trained with (its ``ctc_proj`` over the encoder
         output).  With a head and ``opt.ctc_weight`` = w > 0 the search is the joint CTC / attention beam search (see
         st_amd.ctc_decode): a token c of the ``ctc_pre_beam`` (default ceil(1.5 beam)) best attention tokens of hypothesis g
-        scores (1 - w) log p_att(c | g) + w (psi(g.c) - psi(g)), psi = the CTC prefix log-probability; every other token -inf."""
+        scores (1 - w) log p_att(c | g) + w (psi(g.c) - psi(g)), psi = the CTC prefix log-probability; every other token -inf.
+        ``lm``: a ``st_amd.ngram.NGramLM`` on ``device`` (``NGramLM....to(device)``) - shallow fusion: with ``opt.lm_weight`` =
+        lambda > 0 (or ``opt.lm_length_bonus`` = beta != 0) every candidate that extends a hypothesis which has not emitted EOS
+        also scores lambda log p_lm(c | g) + beta (st_ngram_score between the pre-beam and the advance).  Without a CTC head (or
+        w = 0) the LM route keeps the pre-beam: it considers the ``ctc_pre_beam`` (default ceil(1.5 beam)) best ATTENTION tokens of
+        every hypothesis, not the whole vocabulary - a token the attention decoder ranks below them is never proposed, whatever
+        the LM thinks of it.  With ``lm=None``, or lambda = 0 and beta = 0, every method launches exactly what it does without."""
         if model is None:
             raise NotImplementedError("Decode(HIP): pass the Transformer instance (the reference's checkpoint loader "
                                       "calls an obsolete constructor and cannot run)")
         self.ctc_weight, self.ctc_pre_beam = ctc_decode.check_options(opt, int(opt.beam_size), ctc_head, model, device)
         self.ctc_head = ctc_head
+        self.lm_weight, self.lm_length_bonus, self.lm_pre_beam = ngram.check_options(
+            opt, lm, model, device, int(opt.beam_size), joint=self.ctc_pre_beam is not None)
+        self.lm = lm
+        self._lm_on = lm is not None and (self.lm_weight > 0.0 or self.lm_length_bonus != 0.0)
         self.opt, self.device = opt, device
         self.model = model.to(device).eval()
         self.max_steps = int(getattr(opt, "max_steps", None) or 100)
@@ -148,7 +160,9 @@ class Decode(object):
         advances."""
         embed = (self.model.decoder._st.emb, self.model.decoder._st.pe, st.x_in) if st.x_in is not None else None
         if st.ctc is not None:     # joint CTC / attention: pre-beam, CTC prefix scores, the joint advance (st_amd.ctc_decode)
-            st.ctc.advance(st, logits, self.model.vocab_size, Constants.EOS, st.anc, st.anc is not None, embed)
+            st.ctc.advance(st, logits, self.model.vocab_size, Constants.EOS, st.anc, st.anc is not None, embed, lm=st.lm)
+        elif st.lm is not None:    # attention + language model: pre-beam, LM scores, the joint advance with weight 0 (st_amd.ngram)
+            st.lm.advance(st, logits, self.model.vocab_size, Constants.EOS, st.anc, st.anc is not None, embed)
         else:
             nv.beam_advance(logits, self.model.vocab_size, st.beam, st.step, Constants.EOS, st.scores, st.tokens, st.done,
                             st.lengths, st.hist_scores, st.back, st.toks, st.order, work=st.beam_work, anc=st.anc,
@@ -176,10 +190,11 @@ class Decode(object):
         cur.wait_stream(self._side)
         return out
 
-    def _init_state(self, src_batch, beam, arena, search=True, ctc=None, encoded=None):
+    def _init_state(self, src_batch, beam, arena, search=True, ctc=None, encoded=None, lm=False):
         """Encoder pass + the device state of a search over ``beam`` hypotheses per utterance (call inside ``arena.scope()``).
         ``ctc`` = (pre-beam width K, weight): also the CTC side of a joint search (st_amd.ctc_decode.CtcSearch).
-        ``encoded`` = (enc, in_rows): the encoder output of this batch, already computed in this scope (None: run the encoder)."""
+        ``encoded`` = (enc, in_rows): the encoder output of this batch, already computed in this scope (None: run the encoder).
+        ``lm``: also the language-model side of the search (st_amd.ngram.LmSearch: the histories [-1, .., -1, BOS])."""
         inputs, in_len = src_batch
         model, dev = self.model, self.device
         B = inputs.shape[0]
@@ -196,6 +211,11 @@ class Decode(object):
         st = _DecodeState()
         st.B, st.beam, st.n = B, beam, n
         st.ctc = None if ctc is None else ctc_decode.CtcSearch(self.ctc_head, enc, in_rows, beam, ctc[0], ctc[1])
+        st.lm = None
+        if lm:
+            w = st.ctc.weight if st.ctc is not None else 0.0
+            st.lm = ngram.LmSearch(self.lm, B, beam, self.lm_weight / (1.0 - w), self.lm_length_bonus / (1.0 - w),
+                                   K=None if st.ctc is not None else self.lm_pre_beam)
         st.chains = dec.row_chains(arena)          # None: the layers do not fit the row-chain kernel
         st.need_c_len = not (dec.d_model // dec.layer_stack[0].slf_attn.n_head == 64 and self.max_steps <= 128)
         st.cross = []
@@ -388,16 +408,33 @@ class Decode(object):
             return self._nbest_rows(src_batch, nbest, arena).float()
 
     @torch.no_grad()
-    def decode_two_pass(self, src_batch, ctc_weight=None, beam=None, n_best=None):
+    def lm_score(self, nbest):
+        """Language-model scores of an n-best list: nbest[b] = up to N label lists WITHOUT EOS -> f32 [B, N], log p_lm(h . EOS) of
+        each (the history starts at BOS), -inf for a missing one (a shorter nbest[b], or None in it).  One st_ngram_score_seq launch
+        over all lists; the positions are summed in fp64 on the device."""
+        if self.lm is None:
+            raise ValueError("lm_score: needs the language model (Decode(..., lm=...))")
+        return ngram.score_lists(self.lm, nbest, Constants.EOS, Constants.BOS)
+
+    @torch.no_grad()
+    def decode_two_pass(self, src_batch, ctc_weight=None, beam=None, n_best=None, lm_weight=None):
         """Two-pass decoding ("attention rescoring"): the encoder once, a CTC prefix beam search for ``beam`` hypotheses
         (``ctc_beam``), their teacher-forced attention scores in one batched pass (``score_nbest``), and the joint score
         (1 - w) log p_att(h . EOS) + w log p_ctc(h) - w = ``ctc_weight``, default ``opt.ctc_weight`` - re-sorted, the ``n_best``
         kept.  -> (all_hyp, all_scores) as decode_batch returns them, EOS closing every list (``align`` takes them as they are).
-        Hypotheses are capped at max_steps - 1 labels."""
+        Hypotheses are capped at max_steps - 1 labels.  With a language model and ``lm_weight`` = lambda (default
+        ``opt.lm_weight``) > 0 or ``opt.lm_length_bonus`` = beta != 0 the score also has lambda log p_lm(h . EOS) + beta (len(h) + 1)
+        (``lm_score``: one more launch)."""
         from st_amd import ctc_beam
         w = float((getattr(self.opt, "ctc_weight", None) or 0.0) if ctc_weight is None else ctc_weight)
         if not 0.0 <= w < 1.0:
             raise ValueError("decode_two_pass: ctc_weight must lie in [0, 1), got %r" % w)
+        lam = float(self.lm_weight if lm_weight is None else lm_weight)
+        if not lam >= 0.0:
+            raise ValueError("decode_two_pass: lm_weight must be >= 0, got %r" % lam)
+        if self.lm is None and lm_weight is not None and lam > 0.0:
+            raise ValueError("decode_two_pass: lm_weight needs the language model (Decode(..., lm=...))")
+        fuse = self.lm is not None and (lam > 0.0 or self.lm_length_bonus != 0.0)
         beam, K, N = self._ctc_widths("decode_two_pass", beam, n_best)
         if self.max_steps < 2:
             raise ValueError("decode_two_pass: max_steps must allow a label and EOS")
@@ -409,7 +446,13 @@ class Decode(object):
             fin = torch.isfinite(ctc_scores)
             nbest = [[h if bool(fin[b, j]) else None for j, h in enumerate(hs)] for b, hs in enumerate(hyps)]
             att = self._nbest_rows(src_batch, nbest, arena, encoded=(enc, in_rows)).cpu()
-        all_hyp, scores = ctc_beam.combine(hyps, ctc_scores, att, w, N, Constants.EOS)
+            extra = None
+            if fuse:
+                lens1 = torch.tensor([[len(h) + 1 for h in hs] for hs in hyps], dtype=torch.float64)
+                extra = self.lm_length_bonus * lens1
+                if lam > 0.0:
+                    extra = extra + lam * self.lm_score(nbest).double().cpu()
+        all_hyp, scores = ctc_beam.combine(hyps, ctc_scores, att, w, N, Constants.EOS, extra=extra)
         return all_hyp, list(scores.to(self.device).unbind(0))
 
     @torch.no_grad()
@@ -477,7 +520,7 @@ class Decode(object):
         arena = arena_of(model)
         with arena.scope():
             st = self._init_state(src_batch, beam, arena,
-                                  ctc=(self.ctc_pre_beam, self.ctc_weight) if self.ctc_pre_beam is not None else None)
+                                  ctc=(self.ctc_pre_beam, self.ctc_weight) if self.ctc_pre_beam is not None else None, lm=self._lm_on)
             S = self.max_steps
 
             def one_step():
