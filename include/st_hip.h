@@ -41,7 +41,7 @@ typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C:
  * ST_EPI_* values; comments, whitespace, parameter names and `const` do not count), computed by native.abi_fingerprint():
  *   change a declaration - importing st_amd.native fails - paste the number its message prints.
  * So it cannot be forgotten, and there is nothing in it to assert by value: no test may spell it out. */
-#define ST_ABI_VERSION 2011967259
+#define ST_ABI_VERSION 1521534093
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -627,6 +627,27 @@ int st_ctc_beam_ws_kib(int B, int T, int beam, int L_cap);
 int st_ctc_beam_search(st_stream_t stream, const int* ids, const float* lp, const float* lpb, const int* off, const int* len, int B,
                        int K, int beam, int blank, int L_cap, int* tokens, int* lens, float* score, void* trace,
                        double* trace_norm, int T_trace);
+
+/* st_ctc_beam_search with an n-gram language model fused into the search (the same kernel body, the same single launch; the trie
+ * arrays child_lo .. oov_logp as for st_ngram_* below, order 2..5, V <= 5120).  A prefix h is ranked by log p_ctc,t(h) + G(h),
+ * G(h) = sum_{i <= |h|} fmaf(scale, lm(h_i | bos, h_1 .. h_{i-1}), bias), lm the back-off score of st_ngram_score (a token without a
+ * unigram: oov_logp; -inf vetoes it; scale = 0: the term is bias, nothing is looked up).  G depends on the labels alone: (pb, pnb)
+ * stay pure CTC numbers and every slot carries one fp32 g - a stay keeps it, an extension p.c gets g(p) + the term of c after the
+ * last order - 1 labels of p (bos before the first, nothing before that), an extension that merges into a beam entry adds CTC mass
+ * only.  Selection keeps the `beam` best total + g, lower candidate number on ties, a rank of -inf never; the frame's normaliser
+ * is the LARGEST CTC total among the kept candidates (with scale = bias = 0 that is the first one: every output is then bit-equal
+ * to st_ctc_beam_search's).  After the last frame, if final_eos, fmaf(scale, lm(eos | h), bias) is added, and the beam is re-sorted
+ * by the last frame's rank + that term, best first, slot order on ties (a rank of -inf - eos vetoed - goes last among the live
+ * prefixes; without the term nothing moves).
+ * tokens / lens / score as st_ctc_beam_search (score: the pure log p_ctc) in that order; fused f32 [B][beam] = G(h) (+ the eos
+ * term), -inf in a dead slot: score + fused is the rank.  trace_g (NULL: not written; needs trace) f32 [B][T_trace][beam]: g of the
+ * slot after frame t, -inf for a dead slot.  -1: a bad shape, scale < 0 / NaN / inf, bias not finite, oov_logp > 0, fused NULL,
+ * trace_g without trace.  Nothing is read from host memory; launches are bit-equal. */
+int st_ctc_beam_search_lm(st_stream_t stream, const int* ids, const float* lp, const float* lpb, const int* off, const int* len, int B,
+                          int K, int beam, int blank, int L_cap, int* tokens, int* lens, float* score, void* trace,
+                          double* trace_norm, int T_trace, const int* child_lo, const int* tok, const float* logp, const float* bo,
+                          int nodes, int V, int order, float oov_logp, int bos, int eos, float scale, float bias, int final_eos,
+                          float* fused, float* trace_g);
 
 /* Back-off n-gram language model for shallow fusion (csrc/st_ngram.hip; st_amd/ngram.py builds the arrays).  The model is a trie
  * keyed in REVERSE - the node of the n-gram (w_1 .. w_m) is reached by w_m, w_{m-1}, .., w_1 - over token ids [0, V), V <= 5120,

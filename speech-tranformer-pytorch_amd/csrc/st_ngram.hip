@@ -11,62 +11,9 @@
 //   m     = depth reached by c, h_1, h_2, ..; logp_m = that node's logp (no unigram: oov_logp, m = 1)  - one walk per candidate
 //   score = logp_m + bo_m + bo_{m+1} + .. + bo_k                           fp32, in that order, additions only
 // so a NumPy float32 emulation (tests/_emul_ngram.py) is bit-equal.
-#include "st_common.cuh"
+#include "st_ngram.cuh"                                    // Trie, find_child, walk_history, score_candidate, trie_ok
 
 namespace {
-
-constexpr int MAX_H = 4;                                   // history tokens of an order-5 model
-
-struct Trie {
-  const int* child_lo; const int* tok; const float* logp; const float* bo; int nodes; int V; float oov;
-};
-
-// the child of `node` with token t (binary search among its sorted children: <= 13 rounds at V = 5120), -1 if there is none
-__device__ __forceinline__ int find_child(const Trie& T, int node, int t) {
-  int lo = max(T.child_lo[node], T.V), hi = min(T.child_lo[node + 1], T.nodes);
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (T.tok[mid] < t) lo = mid + 1; else hi = mid;
-  }
-  return (lo < min(T.child_lo[node + 1], T.nodes) && T.tok[lo] == t) ? lo : -1;
-}
-
-// h[0] = the most recent token; -> k = the number of valid tokens (the history ends at the first id outside [0, V)) and
-// bo[j - 1] = the back-off of the context of length j, j = 1 .. k
-__device__ __forceinline__ int walk_history(const Trie& T, const int (&h)[MAX_H], int H, float (&bo)[MAX_H]) {
-  int k = 0;
-  while (k < H && h[k] >= 0 && h[k] < T.V) ++k;
-  int node = -1;
-#pragma unroll
-  for (int j = 0; j < MAX_H; ++j) {
-    bo[j] = 0.f;
-    if (j < k && (j == 0 || node >= 0)) {
-      node = j == 0 ? h[0] : find_child(T, node, h[j]);
-      if (node >= 0) bo[j] = T.bo[node];
-    }
-  }
-  return k;
-}
-
-__device__ __forceinline__ float score_candidate(const Trie& T, int c, const int (&h)[MAX_H], int k, const float (&bo)[MAX_H]) {
-  if (c < 0 || c >= T.V) return -INFINITY;
-  float val = T.logp[c];
-  int m = 1, node = c;
-  if (val == INFINITY) {
-    val = T.oov;                                           // no unigram (and then no longer n-gram ends in c)
-  } else {
-    for (int j = 0; j < k; ++j) {
-      node = find_child(T, node, h[j]);
-      if (node < 0) break;
-      val = T.logp[node];
-      m = j + 2;
-    }
-  }
-#pragma unroll
-  for (int j = 1; j <= MAX_H; ++j)
-    if (j >= m && j <= k) val += bo[j - 1];
-  return val;
-}
 
 // ---- st_ngram_score: one wave (= one workgroup) per hypothesis row, lane j = candidate j.  The row index is the workgroup's,
 //      so the history and its back-off walk are uniform: one walk per wave, through the scalar unit
@@ -129,10 +76,6 @@ __global__ __launch_bounds__(256) void ngram_score_seq_kernel(Trie T, int H, con
   float bo[MAX_H];
   const int k = walk_history(T, h, H, bo);
   out[e] = score_candidate(T, row[t], h, k, bo);
-}
-
-bool trie_ok(const int* child_lo, const int* tok, const float* logp, const float* bo, int nodes, int V, int order) {
-  return child_lo && tok && logp && bo && V > 0 && V <= 5120 && nodes >= V && order >= 2 && order <= MAX_H + 1;
 }
 
 }  // namespace

@@ -5,8 +5,16 @@
 numbers (no further pass over the logits: the row's log-sum-exp is logit(best) - lp(best)) and searches all utterances with ONE
 ``st_ctc_beam_search`` launch (csrc/st_ctc_beam.hip: one wave per utterance; prefixes are merged by their labels).  The decoder is
 never touched.  ``combine`` is the host side of ``Decode.decode_two_pass``: the joint score of every first-pass hypothesis from
-its CTC and its teacher-forced attention score, re-sorted."""
+its CTC and its teacher-forced attention score, re-sorted.
+
+With ``lm`` (a ``st_amd.ngram.NGramLM`` on the device) and a weight, the search itself ranks by log p_ctc + lambda log p_lm + beta
+|h| every frame (``st_ctc_beam_search_lm``: the same single launch); ``NBest.fused`` is then the LM side of the rank,
+lambda log p_lm(h . EOS) + beta (|h| + 1) with ``final_eos``, and ``score`` stays the pure log p_ctc."""
+import math
+
 import torch
+
+import transformer.Constants as Constants
 
 from . import ctc_decode
 from . import native as nv
@@ -18,12 +26,20 @@ MAX_V = 5120              # st_beam_pre_beam's vocabulary limit
 class NBest(object):
     """Device tensors of one searched batch: ``tokens`` i32 [B, N, L_cap] (-1 past a length), ``lens`` i32 [B, N], ``score`` f32
     [B, N] - log p_ctc of the label prefix summed over the alignments the search kept; best first, -inf where an utterance has
-    fewer than N live prefixes."""
+    fewer than N live prefixes.  ``fused`` f32 [B, N]: None for an LM-less search, else the language-model side of the rank the
+    search sorted by (score + fused), -inf in a dead slot."""
 
-    __slots__ = ("tokens", "lens", "score")
+    __slots__ = ("tokens", "lens", "score", "fused")
 
-    def __init__(self, tokens, lens, score):
-        self.tokens, self.lens, self.score = tokens, lens, score
+    def __init__(self, tokens, lens, score, fused=None):
+        self.tokens, self.lens, self.score, self.fused = tokens, lens, score, fused
+
+    def head(self, N):
+        """The N best of every utterance."""
+        if N >= self.tokens.shape[1]:
+            return self
+        return NBest(self.tokens[:, :N].contiguous(), self.lens[:, :N].contiguous(), self.score[:, :N].contiguous(),
+                     None if self.fused is None else self.fused[:, :N].contiguous())
 
     def lists(self):
         """-> (labels[b][j]: the label list of hypothesis j of utterance b, scores: f32 [B, N] on the host).  One host read."""
@@ -60,9 +76,31 @@ def label_capacity(t_max, max_len=None):
     return max(1, min(cap, int(t_max)))
 
 
+def check_lm(lm, lm_weight, lm_length_bonus, V=None, device=None, who="ctc_beam"):
+    """-> (lambda, beta, fused: whether the search runs with the model); ValueError for a weight < 0 / not finite, a weight without
+    ``lm``, or a model that does not fit (vocabulary, device)."""
+    lam = float(lm_weight or 0.0)
+    beta = float(lm_length_bonus or 0.0)
+    if not lam >= 0.0 or not math.isfinite(lam) or not math.isfinite(beta):
+        raise ValueError("%s: lm_weight must be a finite number >= 0 (got %r), lm_length_bonus finite (got %r)" % (who, lam, beta))
+    if lam == 0.0 and beta == 0.0:
+        return lam, beta, False
+    if lm is None:
+        raise ValueError("%s: lm_weight %r / lm_length_bonus %r need a language model (lm=...)" % (who, lam, beta))
+    if lm.trie is None:
+        raise ValueError("%s: the language model has no device trie - pass lm.to(device)" % who)
+    if V is not None and lm.V != V:
+        raise ValueError("%s: the language model's vocabulary %d differs from the head's %d" % (who, lm.V, V))
+    if device is not None and torch.device(lm.trie.device).type != torch.device(device).type:
+        raise ValueError("%s: the language model lives on %s, the rows on %s - pass lm.to(device)" % (who, lm.trie.device, device))
+    return lam, beta, True
+
+
 @torch.no_grad()
-def search_logits(logits, V, in_rows, blank, beam, K, L_cap):
-    """The search over the head's logits f32 [R, >= V] -> NBest with N = beam."""
+def search_logits(logits, V, in_rows, blank, beam, K, L_cap, lm=None, lm_weight=0.0, lm_length_bonus=0.0, final_eos=True):
+    """The search over the head's logits f32 [R, >= V] -> NBest with N = beam.  ``lm`` + ``lm_weight`` (lambda) / ``lm_length_bonus``
+    (beta): the fused search; without a model, or with both 0, the launches are the LM-less ones."""
+    lam, beta, fuse = check_lm(lm, lm_weight, lm_length_bonus, V, logits.device)
     dev, R, B = logits.device, logits.shape[0], in_rows.B
     ids = torch.empty(R, K, dtype=I32, device=dev)
     lp = torch.empty(R, K, dtype=F32, device=dev)
@@ -72,22 +110,29 @@ def search_logits(logits, V, in_rows, blank, beam, K, L_cap):
     tokens = torch.empty(B, beam, L_cap, dtype=I32, device=dev)
     lens = torch.empty(B, beam, dtype=I32, device=dev)
     score = torch.empty(B, beam, dtype=F32, device=dev)
-    nv.ctc_beam_search(ids, lp, lpb, in_rows.off, in_rows.len, blank, tokens, lens, score)
-    return NBest(tokens, lens, score)
+    if not fuse:
+        nv.ctc_beam_search(ids, lp, lpb, in_rows.off, in_rows.len, blank, tokens, lens, score)
+        return NBest(tokens, lens, score)
+    fused = torch.empty(B, beam, dtype=F32, device=dev)
+    nv.ctc_beam_search_lm(ids, lp, lpb, in_rows.off, in_rows.len, blank, tokens, lens, score, lm.trie, Constants.BOS, Constants.EOS,
+                          lam, beta, fused, final_eos=final_eos)
+    return NBest(tokens, lens, score, fused)
 
 
 @torch.no_grad()
-def search_rows(head, enc, in_rows, beam, pre_beam=None, n_best=None, max_len=None):
+def search_rows(head, enc, in_rows, beam, pre_beam=None, n_best=None, max_len=None, lm=None, lm_weight=0.0, lm_length_bonus=0.0,
+                final_eos=True):
     """head: the ``transformer.Loss.CTCAttentionLoss`` of a joint model; enc bf16 [sum(len), d] + in_rows: the packed encoder
     output (``Encoder.forward_rows``) -> NBest of the ``n_best`` (default ``beam``) best label prefixes per utterance.
-    ``pre_beam`` (default ``beam``): classes considered per row; ``max_len``: label capacity (default min(255, longest utterance))."""
+    ``pre_beam`` (default ``beam``): classes considered per row; ``max_len``: label capacity (default min(255, longest utterance)).
+    ``lm``, ``lm_weight``, ``lm_length_bonus``, ``final_eos``: the n-gram model fused into the search (default: off)."""
     V = head.ctc_proj.weight.shape[0]
     beam, K, N = check_widths(V, beam, pre_beam, n_best)
     L_cap = label_capacity(in_rows.max_len, max_len)
-    out = search_logits(ctc_decode.head_logits(head, enc), V, in_rows, int(head.blank), beam, K, L_cap)
-    if N < beam:
-        out = NBest(out.tokens[:, :N].contiguous(), out.lens[:, :N].contiguous(), out.score[:, :N].contiguous())
-    return out
+    check_lm(lm, lm_weight, lm_length_bonus, V, enc.device)                     # (before any launch)
+    out = search_logits(ctc_decode.head_logits(head, enc), V, in_rows, int(head.blank), beam, K, L_cap, lm, lm_weight, lm_length_bonus,
+                        final_eos)
+    return out.head(N)
 
 
 def combine(hyps, ctc_scores, att_scores, weight, n_best, eos, extra=None):

@@ -1150,12 +1150,8 @@ def ctc_beam_ws_bytes(B, T_max, beam, L_cap) -> int:
     return kib * 1024
 
 
-def ctc_beam_search(ids, lp, lpb, off, length, blank, tokens, lens, score, trace=None, trace_norm=None):
-    """CTC prefix beam search of B utterances in one launch - see st_ctc_beam_search.  ids i32 / lp f32 [R, K] (st_beam_pre_beam
-    over the CTC head's logits), lpb f32 [R], off / length i32 [B] (device: capturable) -> tokens i32 [B, beam, L_cap] (-1 past a
-    length), lens i32 [B, beam], score f32 [B, beam] (best first; -inf in the slots past the live prefixes).  ``trace`` u8
-    [B, T_trace, beam, 16] + ``trace_norm`` f64 [B, T_trace]: the per-frame records of the beam (both or neither)."""
-    who = "ctc_beam_search"
+def _ctc_beam_args(who, ids, lp, lpb, off, length, blank, tokens, lens, score, trace, trace_norm):
+    """The argument checks st_ctc_beam_search and st_ctc_beam_search_lm share -> (B, R, K, beam, L_cap, T_trace)."""
     if ids.dim() != 2 or ids.dtype != I32 or not ids.is_contiguous():
         raise ValueError("%s: ids must be a contiguous i32 [R, K] tensor, got %s %s" % (who, ids.dtype, tuple(ids.shape)))
     R, K = ids.shape
@@ -1189,11 +1185,47 @@ def ctc_beam_search(ids, lp, lpb, off, length, blank, tokens, lens, score, trace
             raise RuntimeError("%s: %s must live on the GPU: the HIP path has no CPU fallback" % (who, name))
     if trace is not None and trace.data_ptr() % 16:
         raise ValueError("%s: trace must be 16-byte aligned" % who)
+    return B, R, K, beam, L_cap, T_trace
+
+
+def ctc_beam_search(ids, lp, lpb, off, length, blank, tokens, lens, score, trace=None, trace_norm=None):
+    """CTC prefix beam search of B utterances in one launch - see st_ctc_beam_search.  ids i32 / lp f32 [R, K] (st_beam_pre_beam
+    over the CTC head's logits), lpb f32 [R], off / length i32 [B] (device: capturable) -> tokens i32 [B, beam, L_cap] (-1 past a
+    length), lens i32 [B, beam], score f32 [B, beam] (best first; -inf in the slots past the live prefixes).  ``trace`` u8
+    [B, T_trace, beam, 16] + ``trace_norm`` f64 [B, T_trace]: the per-frame records of the beam (both or neither)."""
+    B, R, K, beam, L_cap, T_trace = _ctc_beam_args("ctc_beam_search", ids, lp, lpb, off, length, blank, tokens, lens, score, trace,
+                                                   trace_norm)
     _tag("ctc_beam_search", B, R, K, beam, io=(ids, lp, lpb, tokens))
     _check(load().st_ctc_beam_search(_stream(), ids.data_ptr(), lp.data_ptr(), lpb.data_ptr(), off.data_ptr(), length.data_ptr(), B, K,
                                      beam, int(blank), L_cap, tokens.data_ptr(), lens.data_ptr(), score.data_ptr(), _p(trace),
                                      _p(trace_norm), T_trace), "st_ctc_beam_search")
     return tokens, lens, score
+
+
+def ctc_beam_search_lm(ids, lp, lpb, off, length, blank, tokens, lens, score, trie, bos, eos, scale, bias, fused, final_eos=True,
+                       trace=None, trace_norm=None, trace_g=None):
+    """``ctc_beam_search`` with the n-gram model ``trie`` (a st_amd.ngram.DeviceTrie) fused into the search - see
+    st_ctc_beam_search_lm: prefixes are ranked by log p_ctc + sum over their labels of (scale lm + bias); ``final_eos``: the EOS
+    term closes the rank.  fused f32 [B, beam]: the LM side of the rank (score stays the pure log p_ctc; score + fused is what the
+    n-best is sorted by).  ``trace_g`` f32 [B, T_trace, beam] (only with ``trace``): g of every slot after every frame."""
+    who = "ctc_beam_search_lm"
+    B, R, K, beam, L_cap, T_trace = _ctc_beam_args(who, ids, lp, lpb, off, length, blank, tokens, lens, score, trace, trace_norm)
+    args = _ngram_trie(trie, who)
+    _dev(fused, F32, (B, beam), who + ": fused")
+    if trace_g is not None:
+        if trace is None:
+            raise ValueError("%s: trace_g goes with trace and trace_norm" % who)
+        _dev(trace_g, F32, (B, T_trace, beam), who + ": trace_g")
+    scale, bias = float(scale), float(bias)
+    if not 0.0 <= scale < float("inf") or not abs(bias) < float("inf"):
+        raise ValueError("%s: scale must be a finite number >= 0 and bias finite, got %r, %r" % (who, scale, bias))
+    _tag("ctc_beam_search_lm", B, R, K, beam, trie.order, io=(ids, lp, lpb, tokens))
+    _check(load().st_ctc_beam_search_lm(_stream(), ids.data_ptr(), lp.data_ptr(), lpb.data_ptr(), off.data_ptr(), length.data_ptr(), B,
+                                        K, beam, int(blank), L_cap, tokens.data_ptr(), lens.data_ptr(), score.data_ptr(), _p(trace),
+                                        _p(trace_norm), T_trace, *args, int(trie.V), int(trie.order), float(trie.oov_logp), int(bos),
+                                        int(eos), scale, bias, 1 if final_eos else 0, fused.data_ptr(), _p(trace_g)),
+           "st_ctc_beam_search_lm")
+    return tokens, lens, score, fused
 
 
 # ---- n-gram language model (csrc/st_ngram.hip; st_amd/ngram.py) ----------------------------------------------------------------------

@@ -41,7 +41,7 @@ class Decode(object):
 
     def __init__(self, opt, device, model=None, ctc_head=None, lm=None):
         """opt: attribute-style (beam_size, n_best, [max_steps=100], [use_graph], [ctc_weight=0.0], [ctc_pre_beam], [lm_weight=0.0],
-        [lm_length_bonus=0.0]); model: a
+        [lm_length_bonus=0.0], [ctc_lm_weight=0.0], [ctc_lm_length_bonus=0.0]); model: a
         transformer.Models.Transformer on ``device`` (the reference loads a checkpoint here with an API that no longer exists).
         ``ctc_head``: the ``transformer.Loss.CTCAttentionLoss`` a joint model was trained with (its ``ctc_proj`` over the encoder
         output).  With a head and ``opt.ctc_weight`` = w > 0 the search is the joint CTC / attention beam search (see
@@ -52,7 +52,9 @@ class Decode(object):
         also scores lambda log p_lm(c | g) + beta (st_ngram_score between the pre-beam and the advance).  Without a CTC head (or
         w = 0) the LM route keeps the pre-beam: it considers the ``ctc_pre_beam`` (default ceil(1.5 beam)) best ATTENTION tokens of
         every hypothesis, not the whole vocabulary - a token the attention decoder ranks below them is never proposed, whatever
-        the LM thinks of it.  With ``lm=None``, or lambda = 0 and beta = 0, every method launches exactly what it does without."""
+        the LM thinks of it.  With ``lm=None``, or lambda = 0 and beta = 0, every method launches exactly what it does without.
+        ``opt.ctc_lm_weight`` / ``opt.ctc_lm_length_bonus`` (default 0: off; they do NOT default to ``opt.lm_weight``): the model
+        fused into the CTC prefix beam search itself - ``ctc_beam`` and the first pass of ``decode_two_pass``."""
         if model is None:
             raise NotImplementedError("Decode(HIP): pass the Transformer instance (the reference's checkpoint loader "
                                       "calls an obsolete constructor and cannot run)")
@@ -62,6 +64,9 @@ class Decode(object):
             opt, lm, model, device, int(opt.beam_size), joint=self.ctc_pre_beam is not None)
         self.lm = lm
         self._lm_on = lm is not None and (self.lm_weight > 0.0 or self.lm_length_bonus != 0.0)
+        from st_amd import ctc_beam
+        self.ctc_lm_weight, self.ctc_lm_length_bonus, _ = ctc_beam.check_lm(
+            lm, getattr(opt, "ctc_lm_weight", None), getattr(opt, "ctc_lm_length_bonus", None), who="Decode: ctc_lm_weight")
         self.opt, self.device = opt, device
         self.model = model.to(device).eval()
         self.max_steps = int(getattr(opt, "max_steps", None) or 100)
@@ -346,20 +351,37 @@ class Decode(object):
         n_best = int(self.opt.n_best if n_best is None else n_best)
         return ctc_beam.check_widths(self.model.vocab_size, beam, getattr(self.opt, "ctc_beam_pre_beam", None), n_best)
 
+    def _first_pass_lm(self, who, lm_weight, lm_length_bonus):
+        """-> (lambda, beta) of the CTC prefix beam search's own LM term: the arguments, else opt.ctc_lm_weight /
+        opt.ctc_lm_length_bonus (default 0: the LM-less search); ValueError for a weight < 0 or a weight without the model."""
+        from st_amd import ctc_beam
+        lam, beta, _ = ctc_beam.check_lm(self.lm, self.ctc_lm_weight if lm_weight is None else lm_weight,
+                                         self.ctc_lm_length_bonus if lm_length_bonus is None else lm_length_bonus, who=who)
+        return lam, beta
+
     @torch.no_grad()
-    def ctc_beam(self, src_batch, beam=None, n_best=None):
+    def ctc_beam(self, src_batch, beam=None, n_best=None, lm_weight=None, lm_length_bonus=None):
         """CTC prefix beam search with the CTC head (st_amd.ctc_beam: the encoder-only first pass): per utterance the ``n_best``
         most probable label lists under the head, each summed over its alignments.  -> (all_hyp, all_scores) shaped as
         decode_batch's: all_hyp[b] = n_best label lists WITHOUT EOS (as ctc_greedy), all_scores[b] = their log-probabilities
         (tensor[n_best], best first; an utterance with fewer live prefixes: [] with -inf).  ``beam`` defaults to
         ``opt.beam_size``, ``n_best`` to ``opt.n_best``; ``opt.ctc_beam_pre_beam`` (default ``beam``): classes considered per row.
-        One encoder pass, one st_ctc_beam_search launch and one host read per batch; the decoder does not run."""
+        One encoder pass, one st_ctc_beam_search launch and one host read per batch; the decoder does not run.
+        ``lm_weight`` = lambda / ``lm_length_bonus`` = beta (default ``opt.ctc_lm_weight`` / ``opt.ctc_lm_length_bonus``, both 0:
+        off) with a language model: the search ranks by log p_ctc(h) + lambda log p_lm(h) + beta |h| EVERY FRAME (the same single
+        launch, st_ctc_beam_search_lm) and, at the end, with the EOS term; the lists come back sorted by that rank and the method
+        returns a third value, ``fused`` [b] = tensor[n_best] of lambda log p_lm(h . EOS) + beta (|h| + 1): all_scores stays the pure
+        log p_ctc, all_scores + fused is the rank."""
         from st_amd import ctc_beam
         beam, K, N = self._ctc_widths("ctc_beam", beam, n_best)
+        lam, beta = self._first_pass_lm("ctc_beam", lm_weight, lm_length_bonus)
         with arena_of(self.model).scope():
             enc, in_rows = self._encode(src_batch)
-            hyps, scores = ctc_beam.search_rows(self.ctc_head, enc, in_rows, beam, K, N).lists()
-        return hyps, list(scores.to(self.device).unbind(0))
+            out = ctc_beam.search_rows(self.ctc_head, enc, in_rows, beam, K, N, lm=self.lm, lm_weight=lam, lm_length_bonus=beta)
+            hyps, scores = out.lists()
+        if out.fused is None:
+            return hyps, list(scores.to(self.device).unbind(0))
+        return hyps, list(scores.to(self.device).unbind(0)), list(out.fused.unbind(0))
 
     def _nbest_rows(self, src_batch, nbest, arena, encoded=None):
         """Teacher-forced log p_att(h . EOS) of nbest[b][j] -> f64 [B, N] on the device (call inside ``arena.scope()``): the decode
@@ -417,15 +439,19 @@ class Decode(object):
         return ngram.score_lists(self.lm, nbest, Constants.EOS, Constants.BOS)
 
     @torch.no_grad()
-    def decode_two_pass(self, src_batch, ctc_weight=None, beam=None, n_best=None, lm_weight=None):
+    def decode_two_pass(self, src_batch, ctc_weight=None, beam=None, n_best=None, lm_weight=None, first_pass_lm_weight=None,
+                        first_pass_lm_length_bonus=None):
         """Two-pass decoding ("attention rescoring"): the encoder once, a CTC prefix beam search for ``beam`` hypotheses
         (``ctc_beam``), their teacher-forced attention scores in one batched pass (``score_nbest``), and the joint score
         (1 - w) log p_att(h . EOS) + w log p_ctc(h) - w = ``ctc_weight``, default ``opt.ctc_weight`` - re-sorted, the ``n_best``
         kept.  -> (all_hyp, all_scores) as decode_batch returns them, EOS closing every list (``align`` takes them as they are).
         Hypotheses are capped at max_steps - 1 labels.  With a language model and ``lm_weight`` = lambda (default
         ``opt.lm_weight``) > 0 or ``opt.lm_length_bonus`` = beta != 0 the score also has lambda log p_lm(h . EOS) + beta (len(h) + 1)
-        (``lm_score``: one more launch)."""
+        (``lm_score``: one more launch).  ``first_pass_lm_weight`` / ``first_pass_lm_length_bonus`` (default ``opt.ctc_lm_weight`` /
+        ``opt.ctc_lm_length_bonus``, both 0: off): the language model inside the first pass as in ``ctc_beam`` - it changes WHICH
+        ``beam`` hypotheses are rescored, nothing else: the final score is the same three-term sum with the pure log p_ctc."""
         from st_amd import ctc_beam
+        lam1, beta1 = self._first_pass_lm("decode_two_pass", first_pass_lm_weight, first_pass_lm_length_bonus)
         w = float((getattr(self.opt, "ctc_weight", None) or 0.0) if ctc_weight is None else ctc_weight)
         if not 0.0 <= w < 1.0:
             raise ValueError("decode_two_pass: ctc_weight must lie in [0, 1), got %r" % w)
@@ -441,7 +467,8 @@ class Decode(object):
         arena = arena_of(self.model)
         with arena.scope():
             enc, in_rows = self._encode(src_batch)
-            first = ctc_beam.search_rows(self.ctc_head, enc, in_rows, beam, K, None, max_len=min(255, self.max_steps - 1))
+            first = ctc_beam.search_rows(self.ctc_head, enc, in_rows, beam, K, None, max_len=min(255, self.max_steps - 1), lm=self.lm,
+                                         lm_weight=lam1, lm_length_bonus=beta1)
             hyps, ctc_scores = first.lists()
             fin = torch.isfinite(ctc_scores)
             nbest = [[h if bool(fin[b, j]) else None for j, h in enumerate(hs)] for b, hs in enumerate(hyps)]
