@@ -176,7 +176,9 @@ int st_gemm_ln(st_stream_t stream, const void* X, int ldx, const void* W, int M,
  * {128, 256, 512}; identical to st_gemm(0, 1, .., ST_EPI_BF16[_ADD]) followed by st_ln_bwd, without dy going to
  * HBM.  Used where a sublayer's input gradient is the previous sublayer's LayerNorm output gradient
  * (SubLayers.py:25-27 -> Attention.py:94 backward, and so on down the stack).  drop_*: the forward dropped the
- * LayerNorm output (st_gemm_ln with drop_where = 2, SubLayers.py:27); the same mask is regenerated here. */
+ * LayerNorm output (st_gemm_ln with drop_where = 2, SubLayers.py:27); the same mask is regenerated here.
+ * tests/test_lnbwd_fp64_gpu.py holds it to fp64 with that one rounding of dy: every row of dx within 1e-2 of its OWN norm (rstd over
+ * six orders of magnitude, a dy that lies in the LayerNorm's null space), dbias = the column sum of dx AS STORED (bf16) within 4.4e-5. */
 int st_gemm_lnbwd(st_stream_t stream, const void* dY, int lddy, const void* W, int ldw, int M, int N, int Kc,
                   const void* aux, int ldaux, const void* xhat, const float* rstd, const float* gamma, void* dx,
                   int lddx, float* dgamma, float* dbeta, float* dbias, const unsigned* drop_seed, unsigned drop_salt,
@@ -262,7 +264,9 @@ int st_row_chain_mask_words(int M, int d_ff);
  * Reference lines: the backward of Attention.py:74-76,92-94 and SubLayers.py:24-28.
  * split_work / split_bytes: as st_row_chain - d_ff / 256 workgroups per row block at decoder-sized M (HEAD replicated, one
  * chunk of the hidden dimension each, the last arriver adds the partial dy in chunk order and runs the second LayerNorm
- * backward and TAIL). */
+ * backward and TAIL).
+ * tests/test_lnbwd_fp64_gpu.py holds every stage to fp64 from the tensors the launch itself wrote for the stage before: delta is formed
+ * from dctx AS STORED (the bf16 values) times O + Ores (within 2.1e-5, element by element), dbias_a / dbias_b from ds_a / ds_b as stored. */
 int st_row_chain_bwd(st_stream_t stream, int M, const void* wfrag, int n_blocks, int next_blocks, int head_blocks,
                      const void* dP, int ldp, const void* G, int ldg, const void* xhat_a, const float* rstd_a,
                      const float* gamma_a, const unsigned* drop_seed, unsigned drop_salt, int drop_thresh, float drop_scale,
@@ -283,7 +287,9 @@ int st_colsum_fold(st_stream_t stream, int n, const float* const* ws, const int*
  * mask (optional bf16 [M,N]): dx is zeroed where mask <= 0 (front-end ReLU,
  * Models.py:28-33) and scaled by mask_scale elsewhere (1/(1-p) of the dropout
  * between that ReLU and the LN).  drop_*: the forward dropped the LayerNorm
- * OUTPUT (st_gemm_ln drop_where = 2): dy is masked / rescaled first. */
+ * OUTPUT (st_gemm_ln drop_where = 2): dy is masked / rescaled first.
+ * tests/test_lnbwd_fp64_gpu.py holds it to fp64: every row of dx within 1e-2 of its OWN norm, dbias summed from the fp32 values BEFORE
+ * their rounding (unlike the fused kernels), a mask of -0.0 or +0.0 zeroes, a positive subnormal keeps. */
 int st_ln_bwd(st_stream_t stream, const void* dy, int lddy, const void* xhat, const float* rstd, const float* gamma,
               const void* mask, void* dx, int lddx, float* dgamma, float* dbeta, float* dbias, int M, int N,
               const unsigned* drop_seed, unsigned drop_salt, int drop_thresh, float drop_scale, float mask_scale);

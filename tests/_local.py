@@ -17,11 +17,13 @@ def rel(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
-def local_figures(got, ref, floor=FLOOR):
+def local_figures(got, ref, floor=FLOOR, own_rows=False):
     """The per-row / per-column (2-D and up: flattened to [-1, last]) or per-element (1-D) error ratios, fp64 on the CPU:
     ``e / max(n, floor * s)`` with e the norm of the difference over the row, n the reference's norm over it and s the
     root-mean-square of those norms.  A row whose reference is small (or zero) is judged against a quarter of the typical
-    row.  Returns a list of (axis name, ratios)."""
+    row.  own_rows: every ROW of a matrix against its own reference norm alone, without the floor (a row whose reference is zero
+    must then be zero; columns keep the floor) - for outputs whose rows span orders of magnitude, where a wrong small row is
+    invisible to the floor.  Returns a list of (axis name, ratios)."""
     got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
     assert got.shape == ref.shape, "shapes differ: got %s, reference %s" % (tuple(got.shape), tuple(ref.shape))
     if got.dim() <= 1:
@@ -33,15 +35,15 @@ def local_figures(got, ref, floor=FLOOR):
     for name, dim in (("row", 1), ("column", 0)):
         e, n = (got - ref).norm(dim=dim), ref.norm(dim=dim)
         s = n.pow(2).mean().sqrt() if n.numel() else n.sum()
-        out.append((name, e / torch.maximum(n, floor * s).clamp_min(1e-300)))
+        out.append((name, e / torch.maximum(n, (0.0 if own_rows and name == "row" else floor) * s).clamp_min(1e-300)))
     return out
 
 
-def check_local(got, ref, tol_local, what, floor=FLOOR):
+def check_local(got, ref, tol_local, what, floor=FLOOR, own_rows=False):
     """Every row and every column (1-D: every element) of ``got`` within ``tol_local`` of the reference, relative to
-    max(its own reference norm, floor * the typical one).  The failure message names the worst row / column, the row's index
+    max(its own reference norm, floor * the typical one); own_rows: rows relative to their own norm alone.  The failure message names the worst row / column, the row's index
     modulo the tile heights, how many fail and the worst ratio.  The figures are printed either way (pytest -s shows them)."""
-    figs = local_figures(got, ref, floor)
+    figs = local_figures(got, ref, floor, own_rows)
     bad = []
     for name, ratio in figs:
         if not ratio.numel():

@@ -15,6 +15,8 @@ import torch
 
 from st_amd import native as nv
 from tests import _emul as em
+from tests import _lnbwd_cases as lnb
+from tests import _lnbwd_ref as lnref
 from tests._local import Guarded, check, check_local, guarded_input, rel  # noqa: F401  (check / rel: also imported from here by other test files)
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +35,8 @@ L_ATTN = dict(O=1.5e-2, lse=2e-3, dQ=2.5e-2, dK=2.5e-2, dV=2e-2, delta=2e-3)
 L_ATTN_DROP = dict(O=2e-2, lse=2e-3, dQ=3e-2, dK=3e-2, dV=2.5e-2, delta=2e-3)         # ... with dropout on the probabilities
 # st_row_chain_bwd: every stage reads the bf16 output of the one before, so a rounding that flips upstream moves
 # everything downstream - most of all delta, a sum of 64 products of such values: 3 x the measured figure where that exceeds the family's
-# 1e-2 (bf16) / 5e-3 (fp32), those otherwise
+# 1e-2 (bf16) / 5e-3 (fp32), those otherwise.  (These are the bounds against the EMULATION; delta and dbias are also held to their
+# own-output references at lnb.L_DELTA / lnb.L_COL - 2.1e-5 and 5.4e-5 - in the test below and in tests/test_lnbwd_fp64_gpu.py.)
 L_CHAIN_BWD = dict(ds_a=1e-2, dH=1e-2, ds_b=1e-2, dctx=1.3e-2, delta=0.17, dga=5e-3, dba=5e-3, dbia=5e-3, dgb=5e-3, dbb=5e-3, dbib=5.3e-3)
 L_CE = 6e-3                       # st_ce_bwd's bf16 gradient
 L_PROBS = 1e-4                    # st_attn_probs' fp32 maps, row by row: the family's tolerance against the emulation
@@ -1942,6 +1945,15 @@ def test_row_chain_bwd_matches_the_separate_kernels(M, variant):
     for n in names:
         tol = 1e-2 if got[n].dtype == BF16 else 5e-3
         check(got[n], ref[n], tol, "row_chain_bwd %s M=%d: %s" % (variant, M, n), tol_local=L_CHAIN_BWD[n])
+    # ... and against the kernel's OWN outputs, where a far tighter reference exists than the emulation's (whose delta comes from its own
+    # dctx, a bf16 flip upstream away: the 0.17 above): delta is the fp64 sum of dctx AS STORED times O + Ores as handed, dbias the
+    # column sum of ds_a / ds_b as stored - at the bounds of tests/_lnbwd_cases.py (tests/LOCAL_BOUNDS.md, "The LayerNorm backward family")
+    what = "row_chain_bwd %s M=%d" % (variant, M)
+    if has_tail:
+        check_local(got["delta"], lnref.delta_of(got["dctx"].detach().cpu(), O, Ores), lnb.L_DELTA, what + ": delta against its own dctx")
+    for n, src, init in (("dbia", "ds_a", 3.0), ("dbib", "ds_b", -3.0)):
+        if n in names:
+            check_local(got[n], lnref.colsum(got[src].detach().cpu()) + init, lnb.L_COL["chain"]["dbias"], what + ": %s against its own %s" % (n, src))
     for gd in guards:
         for n in gd:
             gd[n].assert_intact("row_chain_bwd %s M=%d: %s" % (variant, M, n))

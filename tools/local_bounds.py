@@ -3,7 +3,9 @@ tests/_emul.py evaluated with fp32 and with fp64 accumulation - same bf16 roundi
 the largest per-row / per-column / per-element ratio of tests/_local.py per family and output; likewise the slow-path attention
 kernels over the cases of tests/test_slow_attention_gpu.py (families "dense" and "probs") and the fast attention kernels at sharp
 scores over the cases of tests/test_sharp_attention_gpu.py (family "sharp"); the LayerNorm statistic off centre, at tiny spread and on
-constant rows over the cases of tests/test_ln_stats_gpu.py (family "ln_stats").  No kernel runs here.
+constant rows over the cases of tests/test_ln_stats_gpu.py (family "ln_stats"); the LayerNorm-backward kernels and backward chains
+against fp64 over the cases of tests/test_lnbwd_fp64_gpu.py (family "ln_bwd": two fp32 evaluations, the common-mode strength of the
+fused kernels, what leaving Ores out moves delta by).  No kernel runs here.
 
     python tools/local_bounds.py            # prints one line per family / output
 """
@@ -21,6 +23,8 @@ for p in (ROOT, os.path.join(ROOT, "speech-tranformer-pytorch_amd")):
 from st_amd import chains, native as nv          # noqa: E402
 from tests import _emul as em                     # noqa: E402
 from tests import _ln_stats as ls                 # noqa: E402
+from tests import _lnbwd_cases as lb              # noqa: E402
+from tests import _lnbwd_ref as lref              # noqa: E402
 from tests import _sharp_attn as sh               # noqa: E402
 from tests import _slow_attn as sa                # noqa: E402
 from tests import test_kernels_gpu as tk          # noqa: E402
@@ -225,6 +229,49 @@ def ln_stats():
                 worst[key] = max(worst.get(key, 0.0), v)
 
 
+def ln_bwd_fp64():
+    """The LayerNorm-backward family over the cases of tests/test_lnbwd_fp64_gpu.py (tests/_lnbwd_cases.py), against the plain fp64
+    reference tests/_lnbwd_ref.py, by two fp32 evaluations: the emulation as it is (CPU) and with every column sum, delta's 64 products
+    and the contraction (chunks of 32) accumulated serially (SERIAL).  Per kernel kind and output the larger figure - L_DELTA and
+    L_COL are 3 x these, capped by the bounds in force; the matrices' rows are judged against their OWN norm.  Then the common-mode
+    candidates of the fused kernels (worst row of any matrix output, to stay below L_BF16 / 3) and what leaving Ores out moves delta by
+    (per case the worst and the median element; the smallest of each over the cases)."""
+    import contextlib
+    import io
+    col = {"dga": "dgamma", "dgb": "dgamma", "dba": "dbeta", "dbb": "dbeta", "dbia": "dbias", "dbib": "dbias"}
+    for be_name, be in (("CPU", lb.CPU), ("SERIAL", lb.SERIAL)):
+        for _, kw in lb.cases():
+            report = []
+            with contextlib.redirect_stdout(io.StringIO()):
+                lb.run(kw, be, report=report, asserted=False)
+            kind = lb.IMPLS[kw["impl"]]["kind"]
+            for _, nm, f, _ in report:
+                for axis, v in f.items():
+                    for key in (("ln_bwd fp64 %s" % kind, col.get(nm, nm), axis), ("ln_bwd fp64 %s %s %s" % (kind, kw["family"], be_name), col.get(nm, nm), axis)):
+                        worst[key] = max(worst.get(key, 0.0), v)
+    for cm in lb.CM_CANDIDATES:
+        for be_name, be in (("CPU", lb.CPU), ("SERIAL", lb.SERIAL)):
+            for _, kw in lb.cases():
+                if kw["family"] != "common-mode" or lb.IMPLS[kw["impl"]]["kind"] == "ln_bwd":
+                    continue
+                c, report = lb.build(cm=cm, **kw), []
+                with contextlib.redirect_stdout(io.StringIO()):
+                    lb.verify(c, lb.launch(c, be), report=report, asserted=False)
+                key = ("ln_bwd fp64 common-mode (%g, %g, %g)" % cm, "any", "row")
+                worst[key] = max([worst.get(key, 0.0)] + [f["row"] for _, _, f, _ in report if "row" in f])
+    lo_max, lo_med = float("inf"), float("inf")
+    for _, kw in lb.cases():
+        c = lb.build(**kw)
+        if c.kind != "chain" or not c.has_tail:
+            continue
+        dctx = lb.launch(c, lb.CPU)["dctx"].view
+        ratio = local_figures(lref.delta_of(dctx, c.O, None), lref.delta_of(dctx, c.O, c.Ores))[0][1]
+        live = ratio[~c.dead.repeat(4)] if c.dead is not None else ratio
+        lo_max, lo_med = min(lo_max, float(live.max())), min(lo_med, float(live.median()))
+    worst[("ln_bwd fp64 delta without Ores (smallest over the cases)", "delta", "worst element")] = lo_max
+    worst[("ln_bwd fp64 delta without Ores (smallest over the cases)", "delta", "median element")] = lo_med
+
+
 def probs():
     """st_attn_probs over the cases of tests/test_slow_attention_gpu.py: the emulation's fp32 maps against the fp64 reference."""
     for kw in sa.probs_cases():
@@ -279,6 +326,7 @@ if __name__ == "__main__":
     probs()
     sharp()
     ln_stats()
+    ln_bwd_fp64()
     losses()
     for (family, name, axis), v in sorted(worst.items()):
         print("%-28s %-8s %-8s worst ratio %.3e   x3 = %.3e" % (family, name, axis, v, 3 * v))
