@@ -41,7 +41,7 @@ typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C:
  * ST_EPI_* values; comments, whitespace, parameter names and `const` do not count), computed by native.abi_fingerprint():
  *   change a declaration - importing st_amd.native fails - paste the number its message prints.
  * So it cannot be forgotten, and there is nothing in it to assert by value: no test may spell it out. */
-#define ST_ABI_VERSION 1521534093
+#define ST_ABI_VERSION 1247213695
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -746,7 +746,7 @@ int st_ce_smooth_bwd(st_stream_t stream, const float* logits, int ldl, int R, in
                      const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
                      const float* denom, const float* lse, const float* sums, const float* grad_out, void* dlogits, int ldd);
 
-/* SpecAugment (Park et al. 2019: time and frequency masks; the time warp is not built) inside the training step.  Masks are
+/* SpecAugment (Park et al. 2019: time and frequency masks; the time warp follows below) inside the training step.  Masks are
  * drawn per utterance from the dropout seed in device memory (drop_seed above), so a captured graph draws new masks on every
  * replay; they are applied by the kernel that converts the features to bf16 rows anyway, so no extra byte moves.
  *
@@ -778,6 +778,47 @@ int st_pack_rows_aug(st_stream_t stream, const float* x, int B, int T, int F, co
 int st_feat_stack_aug(st_stream_t stream, const float* x, int B, int T, int F, const int* in_len, const float* stats, int left,
                       int right, int interval, const int* out_off, const int* out_len, int max_out_len, void* out, int ld,
                       const int* table, int n_time, int n_freq);
+
+/* SpecAugment's time warp (csrc/st_timewarp.hip): the utterance's time axis is resampled by a piecewise linear map that moves
+ * one source frame by up to time_warp = W frames and keeps both ends fixed.  Integers only up to the blend, so
+ * tests/_timewarp_ref.py restates it exactly.  n = the utterance's T_raw, as st_specaug_plan computes it.
+ *
+ * The draw.  key as above; wkey = hash32(key ^ 0x77617270); bits_d = hash32((b * 2 + d) ^ wkey) for d in {0, 1} - counters and
+ * key of its own: the masks of a policy do not depend on W.
+ *   W < 1 or n < 2 W + 3:  the utterance is not warped, its entry is (0, 0);
+ *   otherwise              c  = W + 1 + pick(bits_0, n - 2 W - 2)     the source frame that moves, W + 1 <= c <= n - 2 - W
+ *                          c' = c - W + pick(bits_1, 2 W + 1)         where it lands,              1 <= c' <= n - 2
+ * The map.  Output frame u (0 <= u < n) shows source position s(u) = num / den:
+ *   u < c':     num = u * c,                                        den = c'
+ *   otherwise:  num = c * (n - 1 - c') + (u - c') * (n - 1 - c),    den = n - 1 - c'
+ *   q = floor(num * 65536 / den),  g = q >> 16,  fr = q & 0xffff;   s(0) = 0, s(c') = c, s(n - 1) = n - 1 exactly; q is
+ *   monotone in u, 0 <= g <= n - 1, and g + 1 <= n - 1 whenever fr > 0.
+ *   frame u = x[g] + (fr / 65536) * (x[g + 1] - x[g]): subtraction, product and sum each rounded to fp32 (no fused
+ *   multiply-add); x[g + 1] is not read when fr == 0, and the frame is then x[g] unchanged.
+ * The kernels compute q in 32 bits (g = num / den, fr = ((num - g * den) << 16) / den), which is the definition while
+ * num < 2^31; the two feature entry points therefore refuse inputs that could hold an utterance of more than 32,767 raw
+ * frames (T * interval > 32767) instead of computing something else.  A table entry outside 1 .. n - 2 counts as (0, 0).
+ * Order, as in the paper: warp first, then the masks - masks live in OUTPUT (warped) coordinates, an element under a mask is
+ * +0.0 and loads nothing.
+ *
+ * st_specaug_plan_warp: ONE launch writes both tables - `table` bit for bit as st_specaug_plan, and warp int32 [B, 2] =
+ * (c, c').  0 <= time_warp <= 32767. */
+int st_specaug_plan_warp(st_stream_t stream, const unsigned* seed, unsigned salt, const int* len, int B, int interval, int right,
+                         int n_time, int time_width, int time_ratio_permille, int n_freq, int freq_width, int mel_bins,
+                         int time_warp, int* table, int* warp);
+/* st_pack_rows_aug with the warp of `warp` applied first.  Row r, slot k show OUTPUT frame u = src(k, r * interval); the
+ * source frames g and g + 1 are fetched from the stacked input itself: raw frame g stands in row r' = ceil(g / interval), slot
+ * left - (r' * interval - g).  That needs right == 0 and left >= interval - 1 (every raw frame below T_raw is in some row);
+ * any other geometry, and T * interval > 32767, return -1.  An utterance with the entry (0, 0) takes exactly the loads and
+ * conversions of st_pack_rows_aug; so does a slot without a source frame. */
+int st_pack_rows_warp(st_stream_t stream, const float* x, int B, int T, int F, const int* off, const int* len, void* out,
+                      const int* table, const int* warp, int n_time, int n_freq, int mel_bins, int left, int right, int interval);
+/* st_feat_stack_aug with the warp applied after CMVN and before stacking, any geometry: each of the two source frames is
+ * normalised with the statistics of the unwarped utterance, then they are blended.  Both tables planned with the raw lengths
+ * in_len (interval 1, right 0).  T > 32767 returns -1. */
+int st_feat_stack_warp(st_stream_t stream, const float* x, int B, int T, int F, const int* in_len, const float* stats, int left,
+                       int right, int interval, const int* out_off, const int* out_len, int max_out_len, void* out, int ld,
+                       const int* table, const int* warp, int n_time, int n_freq);
 
 /* Exchange two fp32 buffers in place (n % 4 == 0, both 16-byte aligned, not overlapping): the averaged weights (st_adam_clip's
  * avg) go under the model and back.  A pointer swap is not possible - parameter views and captured graphs hold addresses into

@@ -15,7 +15,8 @@ def stack_frames(x: torch.Tensor, lengths: torch.Tensor, left: int, right: int, 
     stats fp32 [B, 2, F+1] per-utterance Kaldi CMVN statistics (or None)
     -> (bf16 row matrix [sum(out_len), F*(1+left+right)], Rows of the subsampled utterances).
     augment (st_amd.augment.SpecAugment, built with this call's F, left, right and frame_rate): its masks are drawn for the
-    raw lengths and applied after CMVN, before stacking - a training-time front-end; None: the unmasked kernel."""
+    raw lengths and applied after CMVN, before stacking - with ``time_warp > 0`` the warp first, also after CMVN, then the
+    masks on the warped utterance - a training-time front-end; None: the unmasked kernel."""
     if right > left:
         raise ValueError("stack_frames: right context > left context is a shape error in the reference (Dataset.py:139)")
     interval = 1 if frame_rate == 10 else int(frame_rate / 10)
@@ -35,6 +36,10 @@ def stack_frames(x: torch.Tensor, lengths: torch.Tensor, left: int, right: int, 
         nv.feat_stack(x.contiguous().float(), in_len, stats, left, right, interval, rows.off, rows.len, rows.max_len, out)
     else:
         table = augment.plan(in_len, stacked=False)
-        nv.feat_stack_aug(x.contiguous().float(), in_len, stats, left, right, interval, rows.off, rows.len, rows.max_len, out,
-                          table, augment.n_time_masks, augment.n_freq_masks)
+        if augment.time_warp > 0:
+            nv.feat_stack_warp(x.contiguous().float(), in_len, stats, left, right, interval, rows.off, rows.len, rows.max_len, out,
+                               table, augment.last_warp, augment.n_time_masks, augment.n_freq_masks)
+        else:
+            nv.feat_stack_aug(x.contiguous().float(), in_len, stats, left, right, interval, rows.off, rows.len, rows.max_len, out,
+                              table, augment.n_time_masks, augment.n_freq_masks)
     return out[:, :width], rows

@@ -1492,6 +1492,85 @@ def feat_stack_aug(x, in_len, stats, left, right, interval, out_off, out_len, ma
     return out
 
 
+WARP_MAX_FRAMES = 32767      # raw frames of an utterance up to which the warp kernels' 32-bit map is the definition (include/st_hip.h)
+
+
+def specaug_plan_warp(seed, salt, length, table, warp, n_time, time_width, time_ratio_permille, n_freq, freq_width, mel_bins,
+                      time_warp, interval=1, right=0):
+    """specaug_plan and the time warp's draw in one launch (st_specaug_plan_warp): ``table`` as specaug_plan writes it, bit for
+    bit, and warp int32 [B, 2] <- (c, c') of every utterance ((0, 0): not warped)."""
+    B = length.numel()
+    if min(int(time_width), int(freq_width)) < 0 or int(mel_bins) < 1 or not 0 <= int(time_ratio_permille) <= 1000:
+        raise ValueError("specaug_plan_warp: time_width %d / freq_width %d >= 0, mel_bins %d >= 1, time_ratio_permille %d in 0 .. 1000"
+                         % (time_width, freq_width, mel_bins, time_ratio_permille))
+    if int(time_warp) != time_warp or not 0 <= int(time_warp) <= WARP_MAX_FRAMES:
+        raise ValueError("specaug_plan_warp: time_warp = %r must be an integer in 0 .. %d" % (time_warp, WARP_MAX_FRAMES))
+    if B > 1 << 24:
+        raise ValueError("specaug_plan_warp: at most 2^24 utterances (the draw's counter is 32 bits wide)")
+    n_time, n_freq, _, right, interval = _specaug_args("specaug_plan_warp", n_time, n_freq, right, right, interval)
+    _dev(table, I32, (B, n_time + n_freq, 2), "specaug_plan_warp: table"), _dev(warp, I32, (B, 2), "specaug_plan_warp: warp")
+    _dev(seed, I32, (1,), "specaug_plan_warp: seed"), _vec(length, I32, B, "specaug_plan_warp: length")
+    _tag("specaug_plan_warp", B, n_time + n_freq, io=(length, table, warp))
+    _check(load().st_specaug_plan_warp(_stream(), seed.data_ptr(), int(salt) & 0xFFFFFFFF, length.data_ptr(), B, interval, right,
+                                       n_time, int(time_width), int(time_ratio_permille), n_freq, int(freq_width), int(mel_bins),
+                                       int(time_warp), table.data_ptr(), warp.data_ptr()), "st_specaug_plan_warp")
+    return table, warp
+
+
+def pack_rows_warp(x, off, length, out, table, warp, n_time, n_freq, mel_bins, left=0, right=0, interval=1):
+    """pack_rows_aug with the time warp of ``warp`` applied before the masks (st_pack_rows_warp): the source frames are read
+    from the stacked rows themselves, so right == 0 and left >= interval - 1."""
+    if x.dim() != 3:
+        raise ValueError("pack_rows_warp: x must be [B, T, F], got %s" % (tuple(x.shape),))
+    B, T, Fd = x.shape
+    mel_bins = int(mel_bins)
+    if mel_bins < 4 or mel_bins % 4:
+        raise ValueError("pack_rows_warp: mel_bins = %d must be a positive multiple of 4 (a 16-byte chunk lies in one context slot)" % mel_bins)
+    n_time, n_freq, left, right, interval = _specaug_args("pack_rows_warp", n_time, n_freq, left, right, interval)
+    if right != 0 or left < interval - 1:
+        raise ValueError("pack_rows_warp: left %d / right %d / interval %d - the warp reads raw frames from the stacked rows, which "
+                         "show every one of them only with right == 0 and left >= interval - 1" % (left, right, interval))
+    if Fd != mel_bins * (1 + left + right):
+        raise ValueError("pack_rows_warp: %d columns are not %d bins x (1 + %d + %d) context slots" % (Fd, mel_bins, left, right))
+    if T * interval > WARP_MAX_FRAMES:
+        raise ValueError("pack_rows_warp: T %d x interval %d > %d raw frames: beyond the kernel's 32-bit map" % (T, interval, WARP_MAX_FRAMES))
+    _dev(table, I32, (B, n_time + n_freq, 2), "pack_rows_warp: table"), _dev(warp, I32, (B, 2), "pack_rows_warp: warp")
+    _dev(x, F32, (B, T, Fd), "pack_rows_warp: x")
+    _vec(off, I32, B, "off"), _vec(length, I32, B, "len")
+    if off.numel() != B or length.numel() != B:
+        raise ValueError("pack_rows_warp: off / len must have one entry per utterance (%d)" % B)
+    _mat(out, BF16, "out", ld=Fd)
+    _tag("pack_rows_warp", out.shape[0], Fd, io=(float(out.shape[0]) * Fd * x.element_size(), out, table, warp))
+    _check(load().st_pack_rows_warp(_stream(), x.data_ptr(), B, T, Fd, off.data_ptr(), length.data_ptr(), out.data_ptr(),
+                                    table.data_ptr(), warp.data_ptr(), n_time, n_freq, mel_bins, left, right, interval),
+           "st_pack_rows_warp")
+    return out
+
+
+def feat_stack_warp(x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out, table, warp, n_time, n_freq):
+    """feat_stack_aug with the time warp of ``warp`` applied after CMVN, before the masks and the stacking (st_feat_stack_warp)."""
+    if x.dim() != 3:
+        raise ValueError("feat_stack_warp: x must be [B, T, F], got %s" % (tuple(x.shape),))
+    B, T, F = x.shape
+    n_time, n_freq, left, right, interval = _specaug_args("feat_stack_warp", n_time, n_freq, left, right, interval)
+    if T > WARP_MAX_FRAMES:
+        raise ValueError("feat_stack_warp: T %d > %d raw frames: beyond the kernel's 32-bit map" % (T, WARP_MAX_FRAMES))
+    _dev(table, I32, (B, n_time + n_freq, 2), "feat_stack_warp: table"), _dev(warp, I32, (B, 2), "feat_stack_warp: warp")
+    _dev(x, F32, (B, T, F), "feat_stack_warp: x")
+    _vec(in_len, I32, B, "in_len"), _vec(out_off, I32, B, "out_off"), _vec(out_len, I32, B, "out_len")
+    _mat(out, BF16, "out")
+    if out.stride(0) < F * (1 + left + right):
+        raise ValueError("feat_stack_warp: out has a leading dimension of %d for %d stacked columns" % (out.stride(0), F * (1 + left + right)))
+    if stats is not None:
+        _dev(stats, F32, (B, 2, F + 1), "feat_stack_warp: stats")
+    _tag("feat_stack_warp", B, T, F)
+    rc = load().st_feat_stack_warp(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), left, right, interval,
+                                   out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(), out.stride(0),
+                                   table.data_ptr(), warp.data_ptr(), n_time, n_freq)
+    _check(rc, "st_feat_stack_warp")
+    return out
+
+
 def row_index(off, length, max_len, row_pos, row_seq=None):
     B = off.numel()
     _vec(off, I32, B, "off"), _vec(length, I32, B, "len")
