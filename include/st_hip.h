@@ -427,7 +427,7 @@ int st_decode_self_attn(st_stream_t stream, const void* qkv, int ldq, void* cach
    inherit (input of st_cache_reorder).  beam <= 16.  `work`: NULL, or ZEROED device scratch of B * beam * beam + 1 + B 8-byte words - with
    it (and V <= 5120) the step runs over B * beam workgroups instead of one per utterance (the `beam` best of every hypothesis
    row; the wave of an utterance's row that finishes last merges them - a ticket per utterance, no second launch); same
-   results.  Only with `work`:
+   results.  A -inf logit: see MASKED LOGITS (at st_ce_fwd).  Only with `work`:
    `anc`: NULL, or the lineage table int32 [B * beam][S] of st_decode_self_attn (S <= 128): the hypothesis placed in slot s
    takes over positions 0 .. *step - 1 of its origin's row of the table and gets the origin's slot as position *step.
    `step_next`: NULL, or `step` itself: the launch also advances the device step counter, *step += 1, once every utterance
@@ -446,7 +446,7 @@ int st_beam_advance(st_stream_t stream, const float* logits, int ldl, int V, int
 
    st_ctc_vocab_lp: logits f32 [R][ldl] (packed encoder rows; utterance b owns rows off[b] .. off[b] + len[b] - 1) ->
    lse[r] = logsumexp(logits[r][:V]) and the vocabulary-major table lpT f32 [B][V][T_cap] = logits - lse (frames t >= len[b]: 0),
-   transposed through LDS tiles. */
+   transposed through LDS tiles.  A -inf logit gives lpT = -inf: see MASKED LOGITS (at st_ce_fwd). */
 int st_ctc_vocab_lp(st_stream_t stream, const float* logits, int ldl, int R, int V, const int* off, const int* len, int B, int T_cap,
                     float* lse, float* lpT);
 
@@ -466,7 +466,7 @@ int st_ctc_prefix_score(st_stream_t stream, const float* lpT, int V, int T_cap, 
                         const unsigned char* done, float* cand_gam, float* cand_psi, float* delta);
 
 /* The attention pre-beam: for each of n rows of decoder logits f32 [n][ldl], log-softmax over the first V columns and its K best
-   (best first, lower id on ties) -> ids int32 [n][K], lp f32 [n][K].  V <= 5120, K <= min(64, V). */
+   (best first, lower id on ties) -> ids int32 [n][K], lp f32 [n][K].  V <= 5120, K <= min(64, V).  -inf logits: MASKED LOGITS. */
 int st_beam_pre_beam(st_stream_t stream, const float* logits, int ldl, int V, int n, int K, int* ids, float* lp);
 
 /* st_beam_advance over beam x K joint candidates: candidate (s, j) = token ids[b * beam + s][j] with score
@@ -544,6 +544,17 @@ int st_grad_norm_blocks(void);
 int st_grad_norm(st_stream_t stream, const float* g, long long n, float* scratch, float* gnorm, float* step,
                  float grad_scale, float* guard, const float* win);
 
+/* MASKED LOGITS - one contract for the eight entry points that form a log-sum-exp over the vocabulary (st_ce_fwd / st_ce_bwd,
+ * st_ce_smooth_fwd / _bwd, st_ce_eval_fwd, st_ctc_gather / st_ctc_dlogits, st_ctc_vocab_lp, st_beam_advance with and without
+ * `work`, st_beam_pre_beam) and for st_ctc_best_path: a logit of -inf is a column of probability zero, PROVIDED the row has a finite
+ * column.  lse is then the log-sum-exp of the finite columns (bit for bit the logit of a row with a single finite column); the
+ * column's log-probability (lp, lpT, a candidate's score) is -inf and it is chosen only after every finite candidate, lower index
+ * first; its softmax and plain-loss gradient are exactly 0, its smoothed gradient exactly bf16(-q[v] * scale).  In a loss, a masked
+ * column the target distribution gives no mass to (q[v] = 0: zero_col, or every column but the target when smooth = 0) costs
+ * nothing - 0 x -inf is 0 - and one it gives mass to makes the row's loss +inf (a masked target included); never NaN.  A row
+ * WITHOUT a finite column is undefined, and so is +inf or NaN anywhere in a row.  Columns >= V are never read by any of them.
+ * tests/test_lse_fp64_gpu.py holds all of this against fp64. */
+
 /* Cross-entropy over ragged logits rows (train.py:40,120: nn.CrossEntropyLoss(ignore_index = 0), mean over the
  * non-ignored tokens).  logits f32 [R, ldl] (V valid columns; padding columns holding -1e30 may be counted as valid),
  * target i64 [R], or - with target_index (i64 [R]) - any i64 vector read as target[target_index[r]] (the padded
@@ -568,7 +579,8 @@ int st_ce_bwd(st_stream_t stream, const float* logits, int ldl, int R, int V, co
  * st_ctc_dlogits: dlogits (bf16 [R, ldd], ldd % 8 == 0) = *grad_out * (roww[b] * softmax(logits[r]) everywhere, columns >= V
  * zero; then column scat[b][k] (i32 [B, C], -1 = none) overwritten with gsmall[b][t][k]) - gsmall (f32 [B, T, C]) being
  * ctc_loss's gradient with respect to lp (which already contains the softmax term at those columns, Graves eq. 16) and
- * roww[b] the weight of utterance b's loss in the reduction (0 for an utterance whose loss is infinite: zero_infinity). */
+ * roww[b] the weight of utterance b's loss in the reduction (0 for an utterance whose loss is infinite: zero_infinity).
+ * -inf logits (masked vocabulary entries): lp = -inf, softmax 0 - see MASKED LOGITS above. */
 int st_ctc_gather(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* rowmap, int T, const int* cols,
                   int C, float* lse, float* lp);
 int st_ctc_dlogits(st_stream_t stream, const float* logits, int ldl, int R, int V, const float* lse, const long long* rowmap, int T,
@@ -736,7 +748,7 @@ int st_clock_probe(st_stream_t stream, long long* out, int n_wg, int iters);
    V is the TRUE vocabulary: columns >= V (the -1e30 padding columns of the vocabulary projection) are never read into
    any sum.  target / target_index / ignore_index / lse / row_loss as st_ce_fwd.  zero_col >= V: refused.
    At (confidence 1, smooth 0, zero_col -1, denom NULL) both calls compute st_ce_fwd / st_ce_bwd bit for bit: the kernels
-   are one body (csrc/st_ce.cuh). */
+   are one body (csrc/st_ce.cuh).  -inf logits: row_loss is +inf when q gives a masked column mass, see MASKED LOGITS (at st_ce_fwd). */
 int st_ce_smooth_fwd(st_stream_t stream, const float* logits, int ldl, int R, int V, const long long* target,
                      const long long* target_index, int ignore_index, float confidence, float smooth, int zero_col,
                      const float* denom, float* lse, float* row_loss, float* sums);
@@ -847,6 +859,7 @@ int st_window_close(st_stream_t stream, float* win, float* out);
  * st_ce_eval_fwd: logits f32 [R, ldl], the first V columns are vocabulary (columns >= V - the -1e30 padding of the vocabulary
  * projection - are never read); target / target_index / ignore_index address the ground truth as in st_ce_fwd; (confidence,
  * smooth, zero_col) is the smoothed target of st_ce_smooth_fwd, (1, 0, -1) the plain loss.  One workgroup per row, one pass.
+ * -inf logits as in st_ce_smooth_fwd (MASKED LOGITS, at st_ce_fwd); a masked column is never the arg-max of a row with a finite one.
  * rows f32 [R, 4] (16-byte aligned), row r = {row_loss, row_nll, row_hit, state}:
  *   state 1 (a counted token): row_loss = st_ce_smooth_fwd's row_loss (the criterion's numerator), row_nll = lse - x[t],
  *           row_hit = 1 if argmax_{v < V} x[v] == t else 0 - among equal maxima the LOWEST column is the arg-max;

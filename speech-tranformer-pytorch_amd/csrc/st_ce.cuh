@@ -32,13 +32,19 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
   const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float* row = logits + (size_t)r * ldl;
   float mx = -INFINITY, sm = 0.f, xs = 0.f;
+  // A masked (-inf) zero column carries no target mass: it stays out of the sum of the logits (0 x -inf is 0 in the loss).  A
+  // finite one is summed and taken back below, as ever.
+  int zskip = -1;
+  if constexpr (Smooth) {
+    if (sp.zero_col >= 0 && sp.zero_col != target[index ? index[r] : r] && row[sp.zero_col] == -INFINITY) zskip = sp.zero_col;
+  }
   for (int v0 = 0; v0 < V; v0 += 256 * 8) {
     float x[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) x[u] = (v0 + u * 256 + tid < V) ? row[v0 + u * 256 + tid] : -INFINITY;
     if constexpr (Smooth) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) xs += (v0 + u * 256 + tid < V) ? x[u] : 0.f;
+      for (int u = 0; u < 8; ++u) xs += (v0 + u * 256 + tid < V && v0 + u * 256 + tid != zskip) ? x[u] : 0.f;
     }
     float bm = x[0];
 #pragma unroll
@@ -79,8 +85,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
       if (t != ignore) {
         const bool hasz = sp.zero_col >= 0 && sp.zero_col != t;
         const float Q = sp.confidence + sp.smooth * (float)(V - 1 - (hasz ? 1 : 0));
-        loss = Q * l - (sp.confidence - sp.smooth) * row[t] - sp.smooth * (redx[0] + redx[1] + redx[2] + redx[3]);
-        if (hasz) loss += sp.smooth * row[sp.zero_col];
+        // (smooth == 0 gives no column but the target any mass: a masked column must not turn 0 x -inf into NaN)
+        const float xsum = sp.smooth != 0.f ? redx[0] + redx[1] + redx[2] + redx[3] : 0.f;
+        loss = Q * l - (sp.confidence - sp.smooth) * row[t] - sp.smooth * xsum;
+        if (hasz && zskip < 0) loss += sp.smooth * row[sp.zero_col];
       }
       row_loss[r] = loss;
     } else {

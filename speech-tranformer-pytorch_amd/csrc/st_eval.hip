@@ -27,6 +27,8 @@ __global__ __launch_bounds__(256) void ce_eval_fwd_kernel(const float* __restric
   // running maximum WITH its column (bv, bi), the exponential sum rescaled to it, the plain sum of the logits
   float bv = -INFINITY, sm = 0.f, xs = 0.f;
   int bi = 0x7fffffff;
+  // (a masked zero column that carries no target mass stays out of the sum of the logits: ce_fwd_kernel<true> in st_ce.cuh)
+  const int zskip = (zero_col >= 0 && zero_col != target[index ? index[r] : r] && row[zero_col] == -INFINITY) ? zero_col : -1;
   for (int v0 = 0; v0 < V; v0 += 256 * 8) {
     float x[8];
 #pragma unroll
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(256) void ce_eval_fwd_kernel(const float* __restric
     for (int u = 0; u < 8; ++u) {      // (columns in ascending order: the first of equal values is kept)
       const int c = v0 + u * 256 + tid;
       if (c < V) {
-        xs += x[u];
+        xs += c != zskip ? x[u] : 0.f;
         if (eval_better(x[u], c, bv, bi)) { bv = x[u]; bi = c; }
       }
     }
@@ -79,8 +81,9 @@ __global__ __launch_bounds__(256) void ce_eval_fwd_kernel(const float* __restric
         const float xt = row[t];
         const bool hasz = zero_col >= 0 && zero_col != t;
         const float Q = confidence + smooth * (float)(V - 1 - (hasz ? 1 : 0));
-        float loss = Q * l - (confidence - smooth) * xt - smooth * (red_x[0] + red_x[1] + red_x[2] + red_x[3]);
-        if (hasz) loss += smooth * row[zero_col];
+        const float xsum = smooth != 0.f ? red_x[0] + red_x[1] + red_x[2] + red_x[3] : 0.f;      // (0 x -inf must not become NaN)
+        float loss = Q * l - (confidence - smooth) * xt - smooth * xsum;
+        if (hasz && zskip < 0) loss += smooth * row[zero_col];
         out[0] = loss;
         out[1] = l - xt;
         out[2] = gi == (int)t ? 1.f : 0.f;

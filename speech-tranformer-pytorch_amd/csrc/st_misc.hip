@@ -1130,7 +1130,7 @@ __global__ __launch_bounds__(256) void ctc_gather_kernel(const float* __restrict
   float mx = -INFINITY, sum = 0.f;
   auto take = [&](float x) {
     if (x > mx) { sum = sum * __expf(mx - x) + 1.f; mx = x; }
-    else sum += __expf(x - mx);
+    else if (mx > -INFINITY) sum += __expf(x - mx);        // (a masked logit before the first finite one: exp(-inf + inf) is NaN)
   };
   if ((ldl & 3) == 0) {
     const f32x4* row4 = reinterpret_cast<const f32x4*>(row);

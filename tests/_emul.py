@@ -608,7 +608,8 @@ def beam_advance(logits, V, beam, step, eos, scores, tokens, done, lengths, hist
     B = scores.shape[0]
     word_lk = torch.log_softmax(logits[:, :V].float(), dim=-1)
     table = (word_lk.view(B, beam, V) + scores.unsqueeze(2)).view(B, beam * V)
-    best_scores, best_flat = table.topk(beam, 1, True, True)
+    best_scores, best_flat = torch.sort(table, dim=1, descending=True, stable=True)      # (lower flat index on ties: the header's rule)
+    best_scores, best_flat = best_scores[:, :beam], best_flat[:, :beam]
     origin = best_flat // V
     token = best_flat - origin * V
     live = ~done

@@ -17,6 +17,23 @@ def _rows(logits, target, V, index, zero_col):
     return V, x, t, tc, hasz
 
 
+def smoothed_sum(x, smooth, zero_col, hasz):
+    """-> (smooth x sum_v x[v], smooth x x[zero_col] hasz): what the row loss subtracts and adds back, as the kernels form the two when
+    a logit is -inf (a column of probability zero): a masked zero column carries no target mass and stays out of both, and smooth == 0
+    gives no column any (0 x -inf is 0, not NaN)."""
+    zero = torch.zeros_like(x[:, 0])
+    if smooth == 0:
+        return zero, zero
+    if zero_col < 0:
+        return smooth * x.sum(-1), zero
+    z = x[:, zero_col]
+    skip = (hasz != 0) & torch.isinf(z) & (z < 0)
+    if not bool(skip.any()):
+        return smooth * x.sum(-1), smooth * z * hasz
+    zs = torch.where(skip, zero, z)
+    return smooth * torch.cat([x[:, :zero_col], zs.view(-1, 1), x[:, zero_col + 1:]], 1).sum(-1), smooth * zs * hasz
+
+
 def ce_smooth_fwd(logits, target, ignore_index, confidence, smooth, zero_col, lse, sums, V=None, index=None, denom=None):
     V, x, t, tc, hasz = _rows(logits, target, V, index, zero_col)
     valid = (t != ignore_index).to(x.dtype)
@@ -24,9 +41,10 @@ def ce_smooth_fwd(logits, target, ignore_index, confidence, smooth, zero_col, ls
     lse.copy_(l)
     xt = x.gather(1, tc).squeeze(1)
     Q = confidence + smooth * (V - 1 - hasz)
-    row = Q * l - (confidence - smooth) * xt - smooth * x.sum(-1)
+    sub, add = smoothed_sum(x, smooth, zero_col, hasz)
+    row = Q * l - (confidence - smooth) * xt - sub
     if zero_col >= 0:
-        row = row + smooth * x[:, zero_col] * hasz
+        row = row + add
     sums[0] = (row * valid).sum()
     sums[1] = valid.sum()
     sums[2] = sums[0] / (sums[1] if denom is None else denom.reshape(-1)[0].to(sums.dtype))

@@ -6,6 +6,7 @@ import contextlib
 import torch
 
 from st_amd import native as nv
+from tests._emul_ce import smoothed_sum
 
 
 def ce_eval_fwd(logits, target, ignore_index, confidence, smooth, zero_col, rows, V=None, index=None):
@@ -21,9 +22,10 @@ def ce_eval_fwd(logits, target, ignore_index, confidence, smooth, zero_col, rows
     l = torch.logsumexp(x, -1)
     xt = x.gather(1, tc).squeeze(1)
     Q = confidence + smooth * (V - 1 - hasz)
-    loss = Q * l - (confidence - smooth) * xt - smooth * x.sum(-1)
+    sub, add = smoothed_sum(x, smooth, zero_col, hasz)
+    loss = Q * l - (confidence - smooth) * xt - sub
     if zero_col >= 0:
-        loss = loss + smooth * x[:, zero_col] * hasz
+        loss = loss + add
     # the FIRST column holding the row's maximum (torch.argmax documents no tie rule)
     cols = torch.arange(V, device=x.device).expand_as(x)
     first = torch.where(x == x.max(-1, keepdim=True).values, cols, torch.full_like(cols, V)).min(-1).values

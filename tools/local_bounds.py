@@ -5,9 +5,11 @@ kernels over the cases of tests/test_slow_attention_gpu.py (families "dense" and
 scores over the cases of tests/test_sharp_attention_gpu.py (family "sharp"); the LayerNorm statistic off centre, at tiny spread and on
 constant rows over the cases of tests/test_ln_stats_gpu.py (family "ln_stats"); the LayerNorm-backward kernels and backward chains
 against fp64 over the cases of tests/test_lnbwd_fp64_gpu.py (family "ln_bwd": two fp32 evaluations, the common-mode strength of the
-fused kernels, what leaving Ores out moves delta by).  No kernel runs here.
+fused kernels, what leaving Ores out moves delta by); the vocabulary log-sum-exp restated in fp32 in two orders over the row families of
+tests/_lse_cases.py (family "lse": the bounds L_LSE and P_REL of tests/test_lse_fp64_gpu.py).  No kernel runs here.
 
     python tools/local_bounds.py            # prints one line per family / output
+    python tools/local_bounds.py lse        # the "lse" family alone, with its table
 """
 import math
 import os
@@ -25,6 +27,7 @@ from tests import _emul as em                     # noqa: E402
 from tests import _ln_stats as ls                 # noqa: E402
 from tests import _lnbwd_cases as lb              # noqa: E402
 from tests import _lnbwd_ref as lref              # noqa: E402
+from tests import _lse_cases as lse_cases         # noqa: E402
 from tests import _sharp_attn as sh               # noqa: E402
 from tests import _slow_attn as sa                # noqa: E402
 from tests import test_kernels_gpu as tk          # noqa: E402
@@ -310,8 +313,26 @@ def losses():
          em.gemm(X, W, torch.zeros(M, N), bias=b, epi=nv.EPI_F32, dtype=F64))
 
 
+def lse_family():
+    """The vocabulary log-sum-exp over every row family and V of tests/_lse_cases.py, restated in fp32 in two orders - the kernels'
+    batched running (max, sum) with a tree merge, and a plain serial max-then-sum, both with __expf as exp2(fp32(d x log2 e)) - against
+    fp64.  Per order and family: the worst |err| - ulp32(|ref|) / 2 (clipped at 0) and the worst relative error of exp(x - lse32) over
+    the entries with p_ref >= 2^-100.  L_LSE and P_REL are 3 x the larger figure of each column."""
+    l_lse, p_rel, rows = lse_cases.measure_bounds()
+    print("%-8s %-12s %-24s %s" % ("order", "family", "|err| - ulp32(|ref|) / 2", "relative error of exp(x - lse32)"))
+    for order, family, wl, wp in rows:
+        print("%-8s %-12s %-24.3e %.3e" % (order, family, wl, wp))
+    print("L_LSE = 3 x %.3e = %.3e (in force %.3e; condition <= log(5120 / 5119) / 4 = %.3e: %s)"
+          % (l_lse / 3, l_lse, lse_cases.L_LSE, lse_cases.L_LSE_MAX, "met" if l_lse <= lse_cases.L_LSE_MAX else "BROKEN"))
+    print("P_REL = 3 x %.3e = %.3e (in force %.3e; condition <= 2^-10 = %.3e: %s)"
+          % (p_rel / 3, p_rel, lse_cases.P_REL, lse_cases.P_REL_MAX, "met" if p_rel <= lse_cases.P_REL_MAX else "BROKEN"))
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
+    if sys.argv[1:] == ["lse"]:
+        lse_family()
+        sys.exit(0)
     attention(tk.ATTN_CASES, "attention")
     attention(tk.DELTA_CASES, "attention")
     attention(tk.PRESCALED_CASES, "attention (prescaled keys)", prescaled=True)
@@ -330,3 +351,4 @@ if __name__ == "__main__":
     losses()
     for (family, name, axis), v in sorted(worst.items()):
         print("%-28s %-8s %-8s worst ratio %.3e   x3 = %.3e" % (family, name, axis, v, 3 * v))
+    lse_family()
