@@ -791,7 +791,7 @@ int st_feat_stack_aug(st_stream_t stream, const float* x, int B, int T, int F, c
                       int right, int interval, const int* out_off, const int* out_len, int max_out_len, void* out, int ld,
                       const int* table, int n_time, int n_freq);
 
-/* SpecAugment's time warp (csrc/st_timewarp.hip): the utterance's time axis is resampled by a piecewise linear map that moves
+/* SpecAugment's time warp (csrc/st_augment.hip): the utterance's time axis is resampled by a piecewise linear map that moves
  * one source frame by up to time_warp = W frames and keeps both ends fixed.  Integers only up to the blend, so
  * tests/_timewarp_ref.py restates it exactly.  n = the utterance's T_raw, as st_specaug_plan computes it.
  *

@@ -1,12 +1,12 @@
-// SpecAugment helpers shared by the kernels of st_augment.hip and st_timewarp.hip: where a stacked row's context slot comes
-// from, whether a raw (frame, bin) lies under a mask of the utterance's table, and where the time warp sends an output frame.
+// Helpers of the feature kernel family (st_augment.hip): where a stacked row's context slot comes from, whether a raw
+// (frame, bin) lies under a mask of the utterance's table, and where the time warp sends an output frame.
 #pragma once
 #include "st_common.cuh"
 
 #define ST_AUG_MAX_MASKS 64      // time + frequency masks of one utterance: the table one workgroup keeps in LDS
 
-// Raw frame that feeds context slot k of the stacked row standing at raw frame t, or -1 when the slot stays zero: the rule of
-// feat_stack_kernel (st_misc.hip; reference Dataset.py:121-143) in closed form.  Slot `left` is the frame itself, slot
+// THE slot rule: raw frame that feeds context slot k of the stacked row standing at raw frame t, or -1 when the slot stays zero
+// (reference Dataset.py:121-143: middle, then left contexts, then right contexts, in closed form).  Slot `left` is the frame itself, slot
 // left - i - 1 the frame i + 1 to the left, slot RIGHT + i + 1 (the reference indexes the right blocks with the right width,
 // :139-141) the frame i + 1 to the right; a later rule overwrites an earlier one, a rule whose frame does not exist writes nothing.
 __device__ __forceinline__ int st_stack_src(int k, int t, int left, int right, int len) {

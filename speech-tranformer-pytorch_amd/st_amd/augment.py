@@ -9,7 +9,7 @@ host.  include/st_hip.h (st_specaug_plan) spells the draw out; tests/_specaug_re
 ``time_warp = W > 0`` adds the paper's first step: per utterance one source frame c moves to c' (|c' - c| <= W), the time
 axis is resampled piecewise linearly with both ends fixed, and the masks are applied to the warped utterance.  The pair is
 drawn by the same plan launch (st_specaug_plan_warp writes both tables) and the resampling happens in the same kernel
-that applies the masks (st_pack_rows_warp / st_feat_stack_warp, csrc/st_timewarp.hip): still two launches per step.
+that applies the masks (st_pack_rows_warp / st_feat_stack_warp, csrc/st_augment.hip): still two launches per step.
 include/st_hip.h (st_specaug_plan_warp) holds the definition, tests/_timewarp_ref.py its restatement.  With
 ``time_warp = 0`` (the default) nothing of this is launched.
 

@@ -1398,24 +1398,13 @@ def attn_dense_bwd(Q, K, V, mask, dO, lse, delta, dQ, dK, dV, B, n_head, Lq, Lk,
     _check(rc, "st_attn_dense_bwd")
 
 
-def feat_stack(x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out):
-    """Raw padded features x fp32 [B, T, F] -> stacked / subsampled / normalised bf16 rows (Dataset.py front-end)."""
-    _dev(x, F32, (None, None, None), "feat_stack: x")
-    B, T, F = x.shape
-    _vec(in_len, I32, B, "in_len"), _vec(out_off, I32, B, "out_off"), _vec(out_len, I32, B, "out_len")
-    _mat(out, BF16, "out")
-    if stats is not None:
-        _dev(stats, F32, (B, 2, F + 1), "feat_stack: stats")
-    _tag("feat_stack", B, T, F)
-    rc = load().st_feat_stack(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), int(left), int(right),
-                              int(interval), out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(),
-                              out.stride(0))
-    _check(rc, "st_feat_stack")
-    return out
+# ---- the feature kernel family (csrc/st_augment.hip): one private function per family, the public wrappers pass their name as
+# ``who``; table None = the variant without masks, warp None = the variant without the time warp ----------------------------------
+WARP_MAX_FRAMES = 32767      # raw frames of an utterance up to which the warp kernels' 32-bit map is the definition (include/st_hip.h)
 
 
 def _specaug_args(who, n_time, n_freq, left, right, interval):
-    """The integer checks the three SpecAugment wrappers share (before any tensor is looked at): mask counts and stacking geometry."""
+    """The integer checks the SpecAugment wrappers share (before any tensor is looked at): mask counts and stacking geometry."""
     n_time, n_freq, left, right, interval = int(n_time), int(n_freq), int(left), int(right), int(interval)
     if n_time < 0 or n_freq < 0 or n_time + n_freq > 64:
         raise ValueError("%s: %d time + %d frequency masks - both counts >= 0 and at most 64 masks in all" % (who, n_time, n_freq))
@@ -1424,151 +1413,146 @@ def _specaug_args(who, n_time, n_freq, left, right, interval):
     return n_time, n_freq, left, right, interval
 
 
+def _given(who, name, t):
+    """A table a public wrapper requires: passed on as None it would select the variant without.  Evaluated as the wrapper's
+    argument, so a missing table is reported before any other bad argument - ValueError, as _dev(None) raised it before."""
+    if t is None:
+        raise ValueError("%s: %s: expected an int32 tensor on the GPU, got None" % (who, name))
+    return t
+
+
+def _tables(who, B, n_masks, table, warp):
+    """The mask table and (warp None: no time warp) the warp table -> the pointers the entry point takes after its other arguments."""
+    _dev(table, I32, (B, n_masks, 2), who + ": table")
+    if warp is None:
+        return (table.data_ptr(),)
+    _dev(warp, I32, (B, 2), who + ": warp")
+    return table.data_ptr(), warp.data_ptr()
+
+
+def _specaug_plan(who, seed, salt, length, table, warp, n_time, time_width, time_ratio_permille, n_freq, freq_width, mel_bins, time_warp,
+                  interval, right):
+    B = length.numel()
+    if min(int(time_width), int(freq_width)) < 0 or int(mel_bins) < 1 or not 0 <= int(time_ratio_permille) <= 1000:
+        raise ValueError("%s: time_width %d / freq_width %d >= 0, mel_bins %d >= 1, time_ratio_permille %d in 0 .. 1000"
+                         % (who, time_width, freq_width, mel_bins, time_ratio_permille))
+    if warp is not None and (int(time_warp) != time_warp or not 0 <= int(time_warp) <= WARP_MAX_FRAMES):
+        raise ValueError("%s: time_warp = %r must be an integer in 0 .. %d" % (who, time_warp, WARP_MAX_FRAMES))
+    if B > 1 << 24:
+        raise ValueError("%s: at most 2^24 utterances (the draw's counter is 32 bits wide)" % who)
+    n_time, n_freq, _, right, interval = _specaug_args(who, n_time, n_freq, right, right, interval)
+    tables = _tables(who, B, n_time + n_freq, table, warp)
+    _dev(seed, I32, (1,), who + ": seed"), _vec(length, I32, B, who + ": length")
+    _tag(who, B, n_time + n_freq, io=(length, table) if warp is None else (length, table, warp))
+    _check(getattr(load(), "st_" + who)(_stream(), seed.data_ptr(), int(salt) & 0xFFFFFFFF, length.data_ptr(), B, interval, right, n_time,
+                                        int(time_width), int(time_ratio_permille), n_freq, int(freq_width), int(mel_bins),
+                                        *((int(time_warp),) if warp is not None else ()), *tables), "st_" + who)
+
+
+def _pack_rows_aug(who, x, off, length, out, table, warp, n_time, n_freq, mel_bins, left, right, interval):
+    if x.dim() != 3:
+        raise ValueError("%s: x must be [B, T, F], got %s" % (who, tuple(x.shape)))
+    B, T, Fd = x.shape
+    mel_bins = int(mel_bins)
+    if mel_bins < 4 or mel_bins % 4:
+        raise ValueError("%s: mel_bins = %d must be a positive multiple of 4 (a 16-byte chunk lies in one context slot)" % (who, mel_bins))
+    n_time, n_freq, left, right, interval = _specaug_args(who, n_time, n_freq, left, right, interval)
+    if warp is not None and (right != 0 or left < interval - 1):
+        raise ValueError("%s: left %d / right %d / interval %d - the warp reads raw frames from the stacked rows, which "
+                         "show every one of them only with right == 0 and left >= interval - 1" % (who, left, right, interval))
+    if Fd != mel_bins * (1 + left + right):
+        raise ValueError("%s: %d columns are not %d bins x (1 + %d + %d) context slots" % (who, Fd, mel_bins, left, right))
+    if warp is not None and T * interval > WARP_MAX_FRAMES:
+        raise ValueError("%s: T %d x interval %d > %d raw frames: beyond the kernel's 32-bit map" % (who, T, interval, WARP_MAX_FRAMES))
+    tables = _tables(who, B, n_time + n_freq, table, warp)
+    _dev(x, F32, (B, T, Fd), who + ": x")
+    _vec(off, I32, B, "off"), _vec(length, I32, B, "len")
+    if off.numel() != B or length.numel() != B:
+        raise ValueError("%s: off / len must have one entry per utterance (%d)" % (who, B))
+    _mat(out, BF16, "out", ld=Fd)
+    _tag(who, out.shape[0], Fd, io=(float(out.shape[0]) * Fd * x.element_size(), out, table) + (() if warp is None else (warp,)))
+    _check(getattr(load(), "st_" + who)(_stream(), x.data_ptr(), B, T, Fd, off.data_ptr(), length.data_ptr(), out.data_ptr(), *tables,
+                                        n_time, n_freq, mel_bins, left, right, interval), "st_" + who)
+    return out
+
+
+def _feat_stack(who, x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out, table=None, warp=None, n_time=0,
+                n_freq=0):
+    if table is None:          # the plain front-end: its geometry is the entry point's to refuse
+        _dev(x, F32, (None, None, None), who + ": x")
+        B, T, F = x.shape
+        left, right, interval = int(left), int(right), int(interval)
+        extra = ()
+    else:
+        if x.dim() != 3:
+            raise ValueError("%s: x must be [B, T, F], got %s" % (who, tuple(x.shape)))
+        B, T, F = x.shape
+        n_time, n_freq, left, right, interval = _specaug_args(who, n_time, n_freq, left, right, interval)
+        if warp is not None and T > WARP_MAX_FRAMES:
+            raise ValueError("%s: T %d > %d raw frames: beyond the kernel's 32-bit map" % (who, T, WARP_MAX_FRAMES))
+        extra = _tables(who, B, n_time + n_freq, table, warp) + (n_time, n_freq)      # what the entry point takes after ld
+        _dev(x, F32, (B, T, F), who + ": x")
+    _vec(in_len, I32, B, "in_len"), _vec(out_off, I32, B, "out_off"), _vec(out_len, I32, B, "out_len")
+    _mat(out, BF16, "out")
+    if table is not None and out.stride(0) < F * (1 + left + right):
+        raise ValueError("%s: out has a leading dimension of %d for %d stacked columns" % (who, out.stride(0), F * (1 + left + right)))
+    if stats is not None:
+        _dev(stats, F32, (B, 2, F + 1), who + ": stats")
+    _tag(who, B, T, F)
+    _check(getattr(load(), "st_" + who)(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), left, right, interval,
+                                        out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(), out.stride(0),
+                                        *extra), "st_" + who)
+    return out
+
+
+def feat_stack(x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out):
+    """Raw padded features x fp32 [B, T, F] -> stacked / subsampled / normalised bf16 rows (Dataset.py front-end)."""
+    return _feat_stack("feat_stack", x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out)
+
+
 def specaug_plan(seed, salt, length, table, n_time, time_width, time_ratio_permille, n_freq, freq_width, mel_bins, interval=1,
                  right=0):
     """SpecAugment's masks of one step (st_specaug_plan): table int32 [B, n_time + n_freq, 2] <- (start, width) of every
     mask, drawn from the device seed (the 1-element int32 tensor of st_amd.rng) and ``salt``.  length: int32 [B] on the device
     - raw frames with (interval 1, right 0), else rows already stacked with that geometry."""
-    B = length.numel()
-    if min(int(time_width), int(freq_width)) < 0 or int(mel_bins) < 1 or not 0 <= int(time_ratio_permille) <= 1000:
-        raise ValueError("specaug_plan: time_width %d / freq_width %d >= 0, mel_bins %d >= 1, time_ratio_permille %d in 0 .. 1000"
-                         % (time_width, freq_width, mel_bins, time_ratio_permille))
-    if B > 1 << 24:
-        raise ValueError("specaug_plan: at most 2^24 utterances (the draw's counter is 32 bits wide)")
-    n_time, n_freq, _, right, interval = _specaug_args("specaug_plan", n_time, n_freq, right, right, interval)
-    _dev(table, I32, (B, n_time + n_freq, 2), "specaug_plan: table")
-    _dev(seed, I32, (1,), "specaug_plan: seed"), _vec(length, I32, B, "specaug_plan: length")
-    _tag("specaug_plan", B, n_time + n_freq, io=(length, table))
-    _check(load().st_specaug_plan(_stream(), seed.data_ptr(), int(salt) & 0xFFFFFFFF, length.data_ptr(), B, interval, right, n_time,
-                                  int(time_width), int(time_ratio_permille), n_freq, int(freq_width), int(mel_bins),
-                                  table.data_ptr()), "st_specaug_plan")
+    _specaug_plan("specaug_plan", seed, salt, length, table, None, n_time, time_width, time_ratio_permille, n_freq, freq_width, mel_bins,
+                  0, interval, right)
     return table
 
 
 def pack_rows_aug(x, off, length, out, table, n_time, n_freq, mel_bins, left=0, right=0, interval=1):
     """pack_rows with the masks of ``table`` applied (st_pack_rows_aug): x fp32 [B, T, mel_bins * (1 + left + right)], rows
     already stacked / subsampled with that geometry."""
-    if x.dim() != 3:
-        raise ValueError("pack_rows_aug: x must be [B, T, F], got %s" % (tuple(x.shape),))
-    B, T, Fd = x.shape
-    mel_bins = int(mel_bins)
-    if mel_bins < 4 or mel_bins % 4:
-        raise ValueError("pack_rows_aug: mel_bins = %d must be a positive multiple of 4 (a 16-byte chunk lies in one context slot)" % mel_bins)
-    n_time, n_freq, left, right, interval = _specaug_args("pack_rows_aug", n_time, n_freq, left, right, interval)
-    if Fd != mel_bins * (1 + left + right):
-        raise ValueError("pack_rows_aug: %d columns are not %d bins x (1 + %d + %d) context slots" % (Fd, mel_bins, left, right))
-    _dev(table, I32, (B, n_time + n_freq, 2), "pack_rows_aug: table")
-    _dev(x, F32, (B, T, Fd), "pack_rows_aug: x")
-    _vec(off, I32, B, "off"), _vec(length, I32, B, "len")
-    if off.numel() != B or length.numel() != B:
-        raise ValueError("pack_rows_aug: off / len must have one entry per utterance (%d)" % B)
-    _mat(out, BF16, "out", ld=Fd)
-    _tag("pack_rows_aug", out.shape[0], Fd, io=(float(out.shape[0]) * Fd * x.element_size(), out, table))
-    _check(load().st_pack_rows_aug(_stream(), x.data_ptr(), B, T, Fd, off.data_ptr(), length.data_ptr(), out.data_ptr(),
-                                   table.data_ptr(), n_time, n_freq, mel_bins, left, right, interval), "st_pack_rows_aug")
-    return out
+    return _pack_rows_aug("pack_rows_aug", x, off, length, out, table, None, n_time, n_freq, mel_bins, left, right, interval)
 
 
 def feat_stack_aug(x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out, table, n_time, n_freq):
     """feat_stack with the masks of ``table`` (planned with the raw lengths) applied after CMVN, before stacking
     (st_feat_stack_aug)."""
-    if x.dim() != 3:
-        raise ValueError("feat_stack_aug: x must be [B, T, F], got %s" % (tuple(x.shape),))
-    B, T, F = x.shape
-    n_time, n_freq, left, right, interval = _specaug_args("feat_stack_aug", n_time, n_freq, left, right, interval)
-    _dev(table, I32, (B, n_time + n_freq, 2), "feat_stack_aug: table")
-    _dev(x, F32, (B, T, F), "feat_stack_aug: x")
-    _vec(in_len, I32, B, "in_len"), _vec(out_off, I32, B, "out_off"), _vec(out_len, I32, B, "out_len")
-    _mat(out, BF16, "out")
-    if out.stride(0) < F * (1 + left + right):
-        raise ValueError("feat_stack_aug: out has a leading dimension of %d for %d stacked columns" % (out.stride(0), F * (1 + left + right)))
-    if stats is not None:
-        _dev(stats, F32, (B, 2, F + 1), "feat_stack_aug: stats")
-    _tag("feat_stack_aug", B, T, F)
-    rc = load().st_feat_stack_aug(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), left, right, interval,
-                                  out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(), out.stride(0),
-                                  table.data_ptr(), n_time, n_freq)
-    _check(rc, "st_feat_stack_aug")
-    return out
-
-
-WARP_MAX_FRAMES = 32767      # raw frames of an utterance up to which the warp kernels' 32-bit map is the definition (include/st_hip.h)
+    return _feat_stack("feat_stack_aug", x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out,
+                       _given("feat_stack_aug", "table", table), None, n_time, n_freq)
 
 
 def specaug_plan_warp(seed, salt, length, table, warp, n_time, time_width, time_ratio_permille, n_freq, freq_width, mel_bins,
                       time_warp, interval=1, right=0):
     """specaug_plan and the time warp's draw in one launch (st_specaug_plan_warp): ``table`` as specaug_plan writes it, bit for
     bit, and warp int32 [B, 2] <- (c, c') of every utterance ((0, 0): not warped)."""
-    B = length.numel()
-    if min(int(time_width), int(freq_width)) < 0 or int(mel_bins) < 1 or not 0 <= int(time_ratio_permille) <= 1000:
-        raise ValueError("specaug_plan_warp: time_width %d / freq_width %d >= 0, mel_bins %d >= 1, time_ratio_permille %d in 0 .. 1000"
-                         % (time_width, freq_width, mel_bins, time_ratio_permille))
-    if int(time_warp) != time_warp or not 0 <= int(time_warp) <= WARP_MAX_FRAMES:
-        raise ValueError("specaug_plan_warp: time_warp = %r must be an integer in 0 .. %d" % (time_warp, WARP_MAX_FRAMES))
-    if B > 1 << 24:
-        raise ValueError("specaug_plan_warp: at most 2^24 utterances (the draw's counter is 32 bits wide)")
-    n_time, n_freq, _, right, interval = _specaug_args("specaug_plan_warp", n_time, n_freq, right, right, interval)
-    _dev(table, I32, (B, n_time + n_freq, 2), "specaug_plan_warp: table"), _dev(warp, I32, (B, 2), "specaug_plan_warp: warp")
-    _dev(seed, I32, (1,), "specaug_plan_warp: seed"), _vec(length, I32, B, "specaug_plan_warp: length")
-    _tag("specaug_plan_warp", B, n_time + n_freq, io=(length, table, warp))
-    _check(load().st_specaug_plan_warp(_stream(), seed.data_ptr(), int(salt) & 0xFFFFFFFF, length.data_ptr(), B, interval, right,
-                                       n_time, int(time_width), int(time_ratio_permille), n_freq, int(freq_width), int(mel_bins),
-                                       int(time_warp), table.data_ptr(), warp.data_ptr()), "st_specaug_plan_warp")
+    _specaug_plan("specaug_plan_warp", seed, salt, length, table, _given("specaug_plan_warp", "warp", warp), n_time, time_width,
+                  time_ratio_permille, n_freq, freq_width, mel_bins, time_warp, interval, right)
     return table, warp
 
 
 def pack_rows_warp(x, off, length, out, table, warp, n_time, n_freq, mel_bins, left=0, right=0, interval=1):
     """pack_rows_aug with the time warp of ``warp`` applied before the masks (st_pack_rows_warp): the source frames are read
     from the stacked rows themselves, so right == 0 and left >= interval - 1."""
-    if x.dim() != 3:
-        raise ValueError("pack_rows_warp: x must be [B, T, F], got %s" % (tuple(x.shape),))
-    B, T, Fd = x.shape
-    mel_bins = int(mel_bins)
-    if mel_bins < 4 or mel_bins % 4:
-        raise ValueError("pack_rows_warp: mel_bins = %d must be a positive multiple of 4 (a 16-byte chunk lies in one context slot)" % mel_bins)
-    n_time, n_freq, left, right, interval = _specaug_args("pack_rows_warp", n_time, n_freq, left, right, interval)
-    if right != 0 or left < interval - 1:
-        raise ValueError("pack_rows_warp: left %d / right %d / interval %d - the warp reads raw frames from the stacked rows, which "
-                         "show every one of them only with right == 0 and left >= interval - 1" % (left, right, interval))
-    if Fd != mel_bins * (1 + left + right):
-        raise ValueError("pack_rows_warp: %d columns are not %d bins x (1 + %d + %d) context slots" % (Fd, mel_bins, left, right))
-    if T * interval > WARP_MAX_FRAMES:
-        raise ValueError("pack_rows_warp: T %d x interval %d > %d raw frames: beyond the kernel's 32-bit map" % (T, interval, WARP_MAX_FRAMES))
-    _dev(table, I32, (B, n_time + n_freq, 2), "pack_rows_warp: table"), _dev(warp, I32, (B, 2), "pack_rows_warp: warp")
-    _dev(x, F32, (B, T, Fd), "pack_rows_warp: x")
-    _vec(off, I32, B, "off"), _vec(length, I32, B, "len")
-    if off.numel() != B or length.numel() != B:
-        raise ValueError("pack_rows_warp: off / len must have one entry per utterance (%d)" % B)
-    _mat(out, BF16, "out", ld=Fd)
-    _tag("pack_rows_warp", out.shape[0], Fd, io=(float(out.shape[0]) * Fd * x.element_size(), out, table, warp))
-    _check(load().st_pack_rows_warp(_stream(), x.data_ptr(), B, T, Fd, off.data_ptr(), length.data_ptr(), out.data_ptr(),
-                                    table.data_ptr(), warp.data_ptr(), n_time, n_freq, mel_bins, left, right, interval),
-           "st_pack_rows_warp")
-    return out
+    return _pack_rows_aug("pack_rows_warp", x, off, length, out, table, _given("pack_rows_warp", "warp", warp), n_time, n_freq, mel_bins, left,
+                          right, interval)
 
 
 def feat_stack_warp(x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out, table, warp, n_time, n_freq):
     """feat_stack_aug with the time warp of ``warp`` applied after CMVN, before the masks and the stacking (st_feat_stack_warp)."""
-    if x.dim() != 3:
-        raise ValueError("feat_stack_warp: x must be [B, T, F], got %s" % (tuple(x.shape),))
-    B, T, F = x.shape
-    n_time, n_freq, left, right, interval = _specaug_args("feat_stack_warp", n_time, n_freq, left, right, interval)
-    if T > WARP_MAX_FRAMES:
-        raise ValueError("feat_stack_warp: T %d > %d raw frames: beyond the kernel's 32-bit map" % (T, WARP_MAX_FRAMES))
-    _dev(table, I32, (B, n_time + n_freq, 2), "feat_stack_warp: table"), _dev(warp, I32, (B, 2), "feat_stack_warp: warp")
-    _dev(x, F32, (B, T, F), "feat_stack_warp: x")
-    _vec(in_len, I32, B, "in_len"), _vec(out_off, I32, B, "out_off"), _vec(out_len, I32, B, "out_len")
-    _mat(out, BF16, "out")
-    if out.stride(0) < F * (1 + left + right):
-        raise ValueError("feat_stack_warp: out has a leading dimension of %d for %d stacked columns" % (out.stride(0), F * (1 + left + right)))
-    if stats is not None:
-        _dev(stats, F32, (B, 2, F + 1), "feat_stack_warp: stats")
-    _tag("feat_stack_warp", B, T, F)
-    rc = load().st_feat_stack_warp(_stream(), x.data_ptr(), B, T, F, in_len.data_ptr(), _p(stats), left, right, interval,
-                                   out_off.data_ptr(), out_len.data_ptr(), int(max_out_len), out.data_ptr(), out.stride(0),
-                                   table.data_ptr(), warp.data_ptr(), n_time, n_freq)
-    _check(rc, "st_feat_stack_warp")
-    return out
+    return _feat_stack("feat_stack_warp", x, in_len, stats, left, right, interval, out_off, out_len, max_out_len, out,
+                       _given("feat_stack_warp", "table", table), _given("feat_stack_warp", "warp", warp), n_time, n_freq)
 
 
 def row_index(off, length, max_len, row_pos, row_seq=None):

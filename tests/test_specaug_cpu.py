@@ -55,7 +55,9 @@ def test_specaug_entry_points_of_the_abi():
     assert {"st_specaug_plan", "st_pack_rows_aug", "st_feat_stack_aug"} <= set(native.SIGNATURES)
     assert "st_augment.hip" in build.SOURCES
     src = open(os.path.join(build.CSRC, "st_augment.hip")).read()
-    assert set(re.findall(r'extern\s+"C"\s+int\s+(st\w+)\s*\(', src)) == {"st_specaug_plan", "st_pack_rows_aug", "st_feat_stack_aug"}
+    assert set(re.findall(r'extern\s+"C"\s+int\s+(st\w+)\s*\(', src)) == {          # the whole feature kernel family
+        "st_feat_stack", "st_specaug_plan", "st_pack_rows_aug", "st_feat_stack_aug", "st_specaug_plan_warp", "st_pack_rows_warp",
+        "st_feat_stack_warp"}
 
 
 # ---- 3. the wrappers raise before any launch -------------------------------------------------------------------------------------

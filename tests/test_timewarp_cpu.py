@@ -44,9 +44,10 @@ def test_timewarp_entry_points_of_the_abi():
     import re
     names = {"st_specaug_plan_warp", "st_pack_rows_warp", "st_feat_stack_warp"}
     assert names <= set(native.SIGNATURES)
-    assert "st_timewarp.hip" in build.SOURCES
-    src = open(os.path.join(build.CSRC, "st_timewarp.hip")).read()
-    assert set(re.findall(r'extern\s+"C"\s+int\s+(st\w+)\s*\(', src)) == names
+    assert "st_augment.hip" in build.SOURCES
+    src = open(os.path.join(build.CSRC, "st_augment.hip")).read()
+    assert set(re.findall(r'extern\s+"C"\s+int\s+(st\w+)\s*\(', src)) == names | {"st_feat_stack", "st_specaug_plan", "st_pack_rows_aug",
+                                                                                   "st_feat_stack_aug"}
     # the table pointers sit where the wrappers pass them
     S = native.SIGNATURES
     assert len(S["st_specaug_plan_warp"]) == len(S["st_specaug_plan"]) + 2
