@@ -41,7 +41,7 @@ typedef struct ihipStream_t* st_stream_t; /* == hipStream_t, spelled in plain C:
  * ST_EPI_* values; comments, whitespace, parameter names and `const` do not count), computed by native.abi_fingerprint():
  *   change a declaration - importing st_amd.native fails - paste the number its message prints.
  * So it cannot be forgotten, and there is nothing in it to assert by value: no test may spell it out. */
-#define ST_ABI_VERSION 1247213695
+#define ST_ABI_VERSION 1672992706
 int st_version(void);
 
 /* Re-read the development switches that choose between a specialised attention kernel and the general one
@@ -697,6 +697,39 @@ int st_ngram_advance(st_stream_t stream, int* hist, int order, const long long* 
                      const unsigned char* done, int eos, int B, int beam);
 int st_ngram_score_seq(st_stream_t stream, const int* child_lo, const int* tok, const float* logp, const float* bo, int nodes, int V,
                        int order, float oov_logp, const int* tokens, const int* lens, int M, int L_cap, int bos, float* out);
+
+/* Contextual biasing: phrases ("hot words") the search and the rescoring reward (csrc/st_bias.hip; st_amd/biasing.py builds the
+ * arrays).  The phrases are an Aho-Corasick automaton of S <= 65536 states over token ids >= 0, phrases of 1..32 tokens: node 0 is
+ * the root, nodes are numbered breadth-first, the children of a node are the consecutive nodes child_lo[node] ..
+ * child_lo[node + 1] - 1 sorted by tok; child_lo i32 [S + 1], tok i32 / fail i32 / cash f32 / phi f32 [S].  fail[node]: the longest
+ * proper suffix of the node's path that is a path (strictly shallower).  cash[node]: the sum of w_p |p| over the phrases that are
+ * suffixes of the node's path; phi[node] = depth x the largest weight of a phrase that continues beyond the node (0: none) - the
+ * provisional reward of a match in progress.  delta(s, c): while s has no child c and s is not the root, s = fail[s]; then the
+ * child if there is one, else the root (any id without an edge, negative ones too, leads to the root).  Appending c in state s adds
+ *   Delta(s, c) = cash[s'] + (phi[s'] - phi[s]),  s' = delta(s, c)     in fp32, in that order;   Delta(s, eos) = -phi[s]
+ * so a list closed by eos has collected exactly the reward of its complete phrase occurrences.  State -1 = frozen (eos emitted).
+ * No table content can hang a kernel or make it read out of bounds: the fail loop runs at most 32 times, states are clamped to
+ * [0, S), child ranges to [0, S].  Device memory only is read: every entry can be captured into a graph.
+ *
+ * st_bias_score: one wave per hypothesis row i < n = B * beam, lane j = candidate cand[i][j] (i32 [n][K], K <= 64); state i32 [n].
+ * raw (NULL: not written) f32 [n][K] = Delta(state[i], cand[i][j]); lp (NULL: not updated) f32 [n][K]: lp = fmaf(scale, Delta, lp)
+ * (scale finite, >= 0; -inf stays -inf).  A frozen row (state < 0): raw 0, lp untouched.  done: NULL or u8 [B] - the rows of a done
+ * utterance are skipped, nothing read or written.
+ *
+ * st_bias_advance: state[i] <- -1 if state[parent[i]] < 0 or tokens[i] == eos, else delta(state[parent[i]], tokens[i]); in place,
+ * one workgroup per utterance (every parent state is read before any is written); parent / tokens: the i64 [n] vectors `order` /
+ * `tokens` of st_beam_advance_joint (a parent outside the utterance counts as the row itself).  done (NULL or u8 [B]): skipped.
+ * beam <= 256.
+ *
+ * st_bias_score_seq: teacher-forced: tokens i32 [M][L_cap], lens i32 [M] -> out f32 [M][L_cap] = Delta of position t from the
+ * root, for t < lens[m]; 0 elsewhere and after an eos.  One lane per list, the arithmetic of st_bias_score. */
+int st_bias_score(st_stream_t stream, const int* child_lo, const int* tok, const int* fail, const float* cash, const float* phi, int S,
+                  const int* state, const int* cand, int n, int K, int beam, const unsigned char* done, int eos, float scale,
+                  float* raw, float* lp);
+int st_bias_advance(st_stream_t stream, const int* child_lo, const int* tok, const int* fail, int S, int* state,
+                    const long long* parent, const long long* tokens, const unsigned char* done, int eos, int B, int beam);
+int st_bias_score_seq(st_stream_t stream, const int* child_lo, const int* tok, const int* fail, const float* cash, const float* phi,
+                      int S, const int* tokens, const int* lens, int M, int L_cap, int eos, float* out);
 
 /* Attention probabilities of ONE attention sublayer, materialised (reference transformer/Attention.py:89,96: the `attns`
  * MultiHeadAttention.forward returns; Models.py:53-54,107-109 collect them under return_attns): P (f32 [B, H, Lq, Lk],

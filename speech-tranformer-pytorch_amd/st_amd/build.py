@@ -23,7 +23,7 @@ LIB = os.path.join(LIBDIR, "libst_hip.so")
 STAMP = LIB + ".srchash"
 SOURCES = ["st_gemm_sym.hip", "st_wgrad.hip", "st_gemm_ws.hip", "st_gemm_ln.hip", "st_gemm_lnbwd.hip", "st_rowchain.hip", "st_attn.hip",
            "st_attn64.hip", "st_attn_bwd64.hip", "st_attn_xs.hip", "st_attn_dense.hip", "st_misc.hip",
-           "st_ctc_decode.hip", "st_ctc_loss.hip", "st_ctc_align.hip", "st_ctc_beam.hip", "st_ngram.hip", "st_loss.hip", "st_augment.hip", "st_optim.hip", "st_eval.hip"]
+           "st_ctc_decode.hip", "st_ctc_loss.hip", "st_ctc_align.hip", "st_ctc_beam.hip", "st_ngram.hip", "st_bias.hip", "st_loss.hip", "st_augment.hip", "st_optim.hip", "st_eval.hip"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-fPIC", "-Wno-unused-result",
          "-I" + os.path.relpath(INCLUDE, CSRC)]      # (relative: hipcc runs in csrc/, and the flags are part of the source hash, which must not depend on where the checkout lies)
 # per-file additions (none today; a kernel that owns all 512 registers per lane would want "-mllvm -amdgpu-mfma-vgpr-form":

@@ -115,16 +115,22 @@ class CtcSearch(object):
         nv.ctc_prefix_score(self.lpT, self.len, self.beam, self.blank, eos, self.ids, self.gam, self.psi, self.last, self.frozen, done,
                             self.cand_gam, self.cand_psi, self.delta)
 
-    def advance(self, st, logits, V, eos, anc, advance_step, embed, lm=None):
+    def advance(self, st, logits, V, eos, anc, advance_step, embed, lm=None, bias=None):
         """One joint Beam.advance for every utterance: pre-beam, prefix scores, joint top-``beam`` + state moves.  ``lm``
         (st_amd.ngram.LmSearch): shallow fusion - the candidates' language-model scores go into ``lp`` before the advance, scaled
-        so that its (1 - w) lp is (1 - w) log p_att + lambda log p_lm + beta, and the histories follow the hypotheses it chose."""
+        so that its (1 - w) lp is (1 - w) log p_att + lambda log p_lm + beta, and the histories follow the hypotheses it chose.
+        ``bias`` (st_amd.biasing.BiasSearch): the candidates' phrase-reward increments go into ``lp`` the same way, and the
+        automaton states follow the hypotheses."""
         nv.beam_pre_beam(logits, V, self.ids, self.lp)
         self.score(eos, st.done)
         if lm is not None:
             lm.score(self.ids, self.lp, st.done, eos)
+        if bias is not None:
+            bias.score(self.ids, self.lp, st.done, eos)
         nv.beam_advance_joint(self.ids, self.lp, self.delta, self.weight, st.beam, st.step, eos, st.scores, st.tokens, st.done,
                               st.lengths, st.hist_scores, st.back, st.toks, st.order, anc=anc, advance_step=advance_step,
                               ticket=self.ticket, embed=embed, ctc=self.state())
         if lm is not None:
             lm.follow(st.order, st.tokens, st.done, eos)
+        if bias is not None:
+            bias.follow(st.order, st.tokens, st.done, eos)

@@ -1302,6 +1302,82 @@ def ngram_score_seq(trie, tokens, lens, bos, out):
     return out
 
 
+# ---- contextual biasing (csrc/st_bias.hip; st_amd/biasing.py) --------------------------------------------------------------------------
+BIAS_MAX_STATES = 65536
+
+
+def _bias_tables(tables, who, values=True):
+    """The leading arguments of the st_bias_* entries from a st_amd.biasing.DeviceAutomaton: (child_lo, tok, fail, [cash, phi,] S)."""
+    S = int(tables.S)
+    if not 1 <= S <= BIAS_MAX_STATES:
+        raise ValueError("%s: %d automaton states outside 1..%d" % (who, S, BIAS_MAX_STATES))
+    args = (_dev(tables.child_lo, I32, (S + 1,), who + ": child_lo"), _dev(tables.tok, I32, (S,), who + ": tok"),
+            _dev(tables.fail, I32, (S,), who + ": fail"))
+    if values:
+        args += (_dev(tables.cash, F32, (S,), who + ": cash"), _dev(tables.phi, F32, (S,), who + ": phi"))
+    return args + (S,)
+
+
+def bias_score(tables, state, cand, done, eos, scale=1.0, raw=None, lp=None):
+    """Phrase-reward increments of every hypothesis's K candidates - see st_bias_score.  state i32 [n] (-1 = frozen), cand i32
+    [n, K], done bool [B] or None (n = B x beam), raw f32 [n, K] or None (the increments), lp f32 [n, K] or None (updated in place:
+    lp = fma(scale, increment, lp))."""
+    who = "bias_score"
+    if cand.dim() != 2 or not 1 <= cand.shape[1] <= 64:
+        raise ValueError("%s: cand must be an i32 [n, K <= 64] tensor, got %s" % (who, tuple(cand.shape)))
+    args = _bias_tables(tables, who)
+    n, K = cand.shape
+    _dev(cand, I32, (n, K), who + ": cand"), _dev(state, I32, (n,), who + ": state")
+    beam = n
+    if done is not None:
+        B = done.numel()
+        if B <= 0 or n % B:
+            raise ValueError("%s: %d rows do not divide into the %d utterances of done" % (who, n, B))
+        _dev(done, torch.bool, (B,), who + ": done")
+        beam = n // B
+    if raw is not None:
+        _dev(raw, F32, (n, K), who + ": raw")
+    if lp is not None:
+        _dev(lp, F32, (n, K), who + ": lp")
+    if not 0.0 <= float(scale) < float("inf"):
+        raise ValueError("%s: scale must be a finite number >= 0, got %r" % (who, scale))
+    _tag("bias_score", n, K, args[-1])
+    _check(load().st_bias_score(_stream(), *args, state.data_ptr(), cand.data_ptr(), n, K, max(beam, 1), _p(done), int(eos),
+                                float(scale), _p(raw), _p(lp)), "st_bias_score")
+
+
+def bias_advance(tables, state, order, tokens, done, eos, beam):
+    """The automaton states of the hypotheses a beam step chose, in place: state[i] <- delta(state[order[i]], tokens[i]), -1 after
+    EOS - see st_bias_advance.  state i32 [n]; order / tokens i64 [n] (st_beam_advance_joint's); done bool [B] or None."""
+    who = "bias_advance"
+    if state.dim() != 1:
+        raise ValueError("%s: state must be an i32 [n] tensor, got %s" % (who, tuple(state.shape)))
+    n, beam = state.shape[0], int(beam)
+    if beam <= 0 or n % beam or beam > 256:
+        raise ValueError("%s: %d rows, beam %d: beam must divide the rows and be <= 256" % (who, n, beam))
+    args = _bias_tables(tables, who, values=False)
+    _dev(state, I32, (n,), who + ": state"), _dev(order, I64, (n,), who + ": order"), _dev(tokens, I64, (n,), who + ": tokens")
+    if done is not None:
+        _dev(done, torch.bool, (n // beam,), who + ": done")
+    _check(load().st_bias_advance(_stream(), *args, state.data_ptr(), order.data_ptr(), tokens.data_ptr(), _p(done), int(eos), n // beam,
+                                  beam), "st_bias_advance")
+
+
+def bias_score_seq(tables, tokens, lens, eos, out):
+    """Teacher-forced phrase-reward increments: tokens i32 [M, L_cap], lens i32 [M] -> out f32 [M, L_cap] = the increment of
+    position t for t < lens[m], 0 elsewhere and after an EOS - see st_bias_score_seq."""
+    who = "bias_score_seq"
+    args = _bias_tables(tables, who)
+    if tokens.dim() != 2:
+        raise ValueError("%s: tokens must be an i32 [M, L_cap] tensor, got %s" % (who, tuple(tokens.shape)))
+    M, L = tokens.shape
+    _dev(tokens, I32, (M, L), who + ": tokens"), _dev(lens, I32, (M,), who + ": lens"), _dev(out, F32, (M, L), who + ": out")
+    _tag("bias_score_seq", M, L, args[-1])
+    _check(load().st_bias_score_seq(_stream(), *args, tokens.data_ptr(), lens.data_ptr(), M, L, int(eos), out.data_ptr()),
+           "st_bias_score_seq")
+    return out
+
+
 def attn_probs(Q, K, q_off, q_len, k_off, k_len, n_head, Lq, Lk, causal, scale, k_prescaled=False, out=None):
     """The attention probabilities of one sublayer, materialised: f32 [B, n_head, Lq, Lk] (zeros at masked keys and in the
     rows of padding positions).  Q, K: bf16 row matrices (column slices of the q | k | v projection are fine).  out: the

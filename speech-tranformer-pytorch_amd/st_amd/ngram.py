@@ -354,17 +354,10 @@ class LmSearch(object):
     to the pre-beam's ``lp``, lp += scale lm + bias - lambda / (1 - w) and beta / (1 - w), because st_beam_advance_joint weighs
     ``lp`` by (1 - w)."""
 
-    def __init__(self, lm, B, beam, scale, bias, K=None):
+    def __init__(self, lm, B, beam, scale, bias):
         self.lm, self.trie, self.B, self.beam = lm, lm.trie, B, beam
         self.scale, self.bias = float(scale), float(bias)
-        dev = lm.trie.device
-        self.hist = initial_history(B * beam, lm.order, dev)
-        if K is not None:                  # the LM-only route owns the pre-beam buffers (the joint one uses CtcSearch's)
-            n = B * beam
-            self.ids = torch.zeros(n, K, dtype=I32, device=dev)
-            self.lp = torch.zeros(n, K, dtype=F32, device=dev)
-            self.zero = torch.zeros(n, K, dtype=F32, device=dev)
-            self.ticket = torch.zeros(1, dtype=I64, device=dev)
+        self.hist = initial_history(B * beam, lm.order, lm.trie.device)
 
     def score(self, ids, lp, done, eos):
         nv.ngram_score(self.trie, self.hist, ids, done, eos, self.scale, self.bias, lp=lp)
@@ -372,15 +365,33 @@ class LmSearch(object):
     def follow(self, order, tokens, done, eos):
         nv.ngram_advance(self.hist, order, tokens, done, eos, self.beam)
 
-    def advance(self, st, logits, V, eos, anc, advance_step, embed):
-        """One Beam.advance of the LM-only route: the K best attention tokens of every hypothesis (NOT the whole vocabulary),
-        their LM scores, st_beam_advance_joint with weight 0 and no CTC state, the histories."""
+
+class PreBeamSearch(object):
+    """The search without a CTC head whose candidates carry extra terms - a language model (LmSearch), a context bias
+    (st_amd.biasing.BiasSearch), or both: it owns the pre-beam buffers (the joint route uses CtcSearch's)."""
+
+    def __init__(self, B, beam, K, device):
+        n = B * beam
+        self.ids = torch.zeros(n, K, dtype=I32, device=device)
+        self.lp = torch.zeros(n, K, dtype=F32, device=device)
+        self.zero = torch.zeros(n, K, dtype=F32, device=device)
+        self.ticket = torch.zeros(1, dtype=I64, device=device)
+
+    def advance(self, st, logits, V, eos, anc, advance_step, embed, lm=None, bias=None):
+        """One Beam.advance of the head-less route: the K best attention tokens of every hypothesis (NOT the whole vocabulary),
+        their LM scores and / or phrase rewards, st_beam_advance_joint with weight 0 and no CTC state, the histories / states."""
         nv.beam_pre_beam(logits, V, self.ids, self.lp)
-        self.score(self.ids, self.lp, st.done, eos)
+        if lm is not None:
+            lm.score(self.ids, self.lp, st.done, eos)
+        if bias is not None:
+            bias.score(self.ids, self.lp, st.done, eos)
         nv.beam_advance_joint(self.ids, self.lp, self.zero, 0.0, st.beam, st.step, eos, st.scores, st.tokens, st.done, st.lengths,
                               st.hist_scores, st.back, st.toks, st.order, anc=anc, advance_step=advance_step, ticket=self.ticket,
                               embed=embed, ctc=None)
-        self.follow(st.order, st.tokens, st.done, eos)
+        if lm is not None:
+            lm.follow(st.order, st.tokens, st.done, eos)
+        if bias is not None:
+            bias.follow(st.order, st.tokens, st.done, eos)
 
 
 @torch.no_grad()

@@ -25,6 +25,7 @@ import math
 import torch
 
 import transformer.Constants as Constants
+from st_amd import biasing
 from st_amd import ctc_decode
 from st_amd import functional as F_
 from st_amd import native as nv
@@ -39,9 +40,9 @@ LN_EPS = 1e-6
 class Decode(object):
     ''' Beam search over a trained Transformer. '''
 
-    def __init__(self, opt, device, model=None, ctc_head=None, lm=None):
+    def __init__(self, opt, device, model=None, ctc_head=None, lm=None, bias=None):
         """opt: attribute-style (beam_size, n_best, [max_steps=100], [use_graph], [ctc_weight=0.0], [ctc_pre_beam], [lm_weight=0.0],
-        [lm_length_bonus=0.0], [ctc_lm_weight=0.0], [ctc_lm_length_bonus=0.0]); model: a
+        [lm_length_bonus=0.0], [ctc_lm_weight=0.0], [ctc_lm_length_bonus=0.0], [bias_weight=1.0]); model: a
         transformer.Models.Transformer on ``device`` (the reference loads a checkpoint here with an API that no longer exists).
         ``ctc_head``: the ``transformer.Loss.CTCAttentionLoss`` a joint model was trained with (its ``ctc_proj`` over the encoder
         output).  With a head and ``opt.ctc_weight`` = w > 0 the search is the joint CTC / attention beam search (see
@@ -54,7 +55,16 @@ class Decode(object):
         every hypothesis, not the whole vocabulary - a token the attention decoder ranks below them is never proposed, whatever
         the LM thinks of it.  With ``lm=None``, or lambda = 0 and beta = 0, every method launches exactly what it does without.
         ``opt.ctc_lm_weight`` / ``opt.ctc_lm_length_bonus`` (default 0: off; they do NOT default to ``opt.lm_weight``): the model
-        fused into the CTC prefix beam search itself - ``ctc_beam`` and the first pass of ``decode_two_pass``."""
+        fused into the CTC prefix beam search itself - ``ctc_beam`` and the first pass of ``decode_two_pass``.
+        ``bias``: a ``st_amd.biasing.ContextBias`` on ``device`` (``ContextBias.from_phrases(...).to(device)``) - contextual biasing:
+        with ``opt.bias_weight`` = b > 0 (default 1; it multiplies every phrase weight) a hypothesis h also scores b x reward(h), the
+        sum of w_p |p| over the occurrences of the phrases in it; while it grows it carries a provisional reward for the phrase in
+        progress, taken back when the match falls through or EOS closes the list (st_bias_score / st_bias_advance around the
+        advance, inside the captured step).  Without a CTC head (or w = 0) the search keeps the pre-beam as with a language model,
+        and on EVERY route a token can only be boosted if the pre-beam proposes it: a phrase token the attention decoder ranks
+        below its ``ctc_pre_beam`` best is never considered, whatever its weight.  ``ctc_beam`` and the first pass of
+        ``decode_two_pass`` are not biased; its rescoring is.  With ``bias=None`` or b = 0 every method launches exactly what it
+        does without.  Each ``decode_batch`` call captures its own step, so a call may follow one with another ``bias`` object."""
         if model is None:
             raise NotImplementedError("Decode(HIP): pass the Transformer instance (the reference's checkpoint loader "
                                       "calls an obsolete constructor and cannot run)")
@@ -67,6 +77,10 @@ class Decode(object):
         from st_amd import ctc_beam
         self.ctc_lm_weight, self.ctc_lm_length_bonus, _ = ctc_beam.check_lm(
             lm, getattr(opt, "ctc_lm_weight", None), getattr(opt, "ctc_lm_length_bonus", None), who="Decode: ctc_lm_weight")
+        self.bias_weight, self.bias_pre_beam = biasing.check_options(opt, bias, model, device, int(opt.beam_size),
+                                                                     joint=self.ctc_pre_beam is not None)
+        self.bias = bias
+        self._bias_on = bias is not None and self.bias_weight > 0.0
         self.opt, self.device = opt, device
         self.model = model.to(device).eval()
         self.max_steps = int(getattr(opt, "max_steps", None) or 100)
@@ -75,6 +89,14 @@ class Decode(object):
         self._side = None
         self.alignment = None     # align(): the device tensors of its last call
         self._warm = False       # a step has run eagerly on this object: later calls capture before their step 0
+
+    def set_bias(self, bias):
+        """Replace the context bias (None: none) for the calls that follow - the per-request phrase list.  Checked as in the
+        constructor; ``decode_batch`` builds its state and captures its step per call, so nothing of the earlier one is reused."""
+        self.bias_weight, self.bias_pre_beam = biasing.check_options(self.opt, bias, self.model, self.device, int(self.opt.beam_size),
+                                                                     joint=self.ctc_pre_beam is not None)
+        self.bias = bias
+        self._bias_on = bias is not None and self.bias_weight > 0.0
 
     # ---- one decoder step for all n = B * beam hypotheses; everything that changes from step to step is DEVICE state ---
     @torch.no_grad()
@@ -165,9 +187,10 @@ class Decode(object):
         advances."""
         embed = (self.model.decoder._st.emb, self.model.decoder._st.pe, st.x_in) if st.x_in is not None else None
         if st.ctc is not None:     # joint CTC / attention: pre-beam, CTC prefix scores, the joint advance (st_amd.ctc_decode)
-            st.ctc.advance(st, logits, self.model.vocab_size, Constants.EOS, st.anc, st.anc is not None, embed, lm=st.lm)
-        elif st.lm is not None:    # attention + language model: pre-beam, LM scores, the joint advance with weight 0 (st_amd.ngram)
-            st.lm.advance(st, logits, self.model.vocab_size, Constants.EOS, st.anc, st.anc is not None, embed)
+            st.ctc.advance(st, logits, self.model.vocab_size, Constants.EOS, st.anc, st.anc is not None, embed, lm=st.lm, bias=st.bias)
+        elif st.pre is not None:   # attention + language model and / or context bias: pre-beam, their terms, the joint advance
+            # with weight 0 (st_amd.ngram.PreBeamSearch)
+            st.pre.advance(st, logits, self.model.vocab_size, Constants.EOS, st.anc, st.anc is not None, embed, lm=st.lm, bias=st.bias)
         else:
             nv.beam_advance(logits, self.model.vocab_size, st.beam, st.step, Constants.EOS, st.scores, st.tokens, st.done,
                             st.lengths, st.hist_scores, st.back, st.toks, st.order, work=st.beam_work, anc=st.anc,
@@ -195,11 +218,12 @@ class Decode(object):
         cur.wait_stream(self._side)
         return out
 
-    def _init_state(self, src_batch, beam, arena, search=True, ctc=None, encoded=None, lm=False):
+    def _init_state(self, src_batch, beam, arena, search=True, ctc=None, encoded=None, lm=False, bias=None):
         """Encoder pass + the device state of a search over ``beam`` hypotheses per utterance (call inside ``arena.scope()``).
         ``ctc`` = (pre-beam width K, weight): also the CTC side of a joint search (st_amd.ctc_decode.CtcSearch).
         ``encoded`` = (enc, in_rows): the encoder output of this batch, already computed in this scope (None: run the encoder).
-        ``lm``: also the language-model side of the search (st_amd.ngram.LmSearch: the histories [-1, .., -1, BOS])."""
+        ``lm``: also the language-model side of the search (st_amd.ngram.LmSearch: the histories [-1, .., -1, BOS]).
+        ``bias``: a ContextBias - also the biasing side of the search (st_amd.biasing.BiasSearch: every state at the root)."""
         inputs, in_len = src_batch
         model, dev = self.model, self.device
         B = inputs.shape[0]
@@ -219,8 +243,14 @@ class Decode(object):
         st.lm = None
         if lm:
             w = st.ctc.weight if st.ctc is not None else 0.0
-            st.lm = ngram.LmSearch(self.lm, B, beam, self.lm_weight / (1.0 - w), self.lm_length_bonus / (1.0 - w),
-                                   K=None if st.ctc is not None else self.lm_pre_beam)
+            st.lm = ngram.LmSearch(self.lm, B, beam, self.lm_weight / (1.0 - w), self.lm_length_bonus / (1.0 - w))
+        st.bias = None
+        if bias is not None:
+            w = st.ctc.weight if st.ctc is not None else 0.0
+            st.bias = biasing.BiasSearch(bias, B, beam, self.bias_weight / (1.0 - w))
+        st.pre = None
+        if st.ctc is None and (st.lm is not None or st.bias is not None):
+            st.pre = ngram.PreBeamSearch(B, beam, self.lm_pre_beam if self.lm_pre_beam is not None else self.bias_pre_beam, dev)
         st.chains = dec.row_chains(arena)          # None: the layers do not fit the row-chain kernel
         st.need_c_len = not (dec.d_model // dec.layer_stack[0].slf_attn.n_head == 64 and self.max_steps <= 128)
         st.cross = []
@@ -439,8 +469,18 @@ class Decode(object):
         return ngram.score_lists(self.lm, nbest, Constants.EOS, Constants.BOS)
 
     @torch.no_grad()
+    def bias_score(self, nbest):
+        """Phrase rewards of an n-best list: nbest[b] = up to N label lists WITHOUT EOS -> f32 [B, N], reward(h) of each (the sum of
+        w_p |p| over the occurrences of the context bias's phrases; NOT multiplied by ``bias_weight``), -inf for a missing one (a
+        shorter nbest[b], or None in it).  One st_bias_score_seq launch over all lists; the positions are summed in fp64 on the
+        device."""
+        if self.bias is None:
+            raise ValueError("bias_score: needs the context bias (Decode(..., bias=...))")
+        return biasing.score_lists(self.bias, nbest, Constants.EOS)
+
+    @torch.no_grad()
     def decode_two_pass(self, src_batch, ctc_weight=None, beam=None, n_best=None, lm_weight=None, first_pass_lm_weight=None,
-                        first_pass_lm_length_bonus=None):
+                        first_pass_lm_length_bonus=None, bias_weight=None):
         """Two-pass decoding ("attention rescoring"): the encoder once, a CTC prefix beam search for ``beam`` hypotheses
         (``ctc_beam``), their teacher-forced attention scores in one batched pass (``score_nbest``), and the joint score
         (1 - w) log p_att(h . EOS) + w log p_ctc(h) - w = ``ctc_weight``, default ``opt.ctc_weight`` - re-sorted, the ``n_best``
@@ -449,7 +489,9 @@ class Decode(object):
         ``opt.lm_weight``) > 0 or ``opt.lm_length_bonus`` = beta != 0 the score also has lambda log p_lm(h . EOS) + beta (len(h) + 1)
         (``lm_score``: one more launch).  ``first_pass_lm_weight`` / ``first_pass_lm_length_bonus`` (default ``opt.ctc_lm_weight`` /
         ``opt.ctc_lm_length_bonus``, both 0: off): the language model inside the first pass as in ``ctc_beam`` - it changes WHICH
-        ``beam`` hypotheses are rescored, nothing else: the final score is the same three-term sum with the pure log p_ctc."""
+        ``beam`` hypotheses are rescored, nothing else: the final score is the same three-term sum with the pure log p_ctc.
+        With a context bias and ``bias_weight`` = b (default ``opt.bias_weight``) > 0 the score also has b x reward(h)
+        (``bias_score``: one more launch); the first pass is not biased."""
         from st_amd import ctc_beam
         lam1, beta1 = self._first_pass_lm("decode_two_pass", first_pass_lm_weight, first_pass_lm_length_bonus)
         w = float((getattr(self.opt, "ctc_weight", None) or 0.0) if ctc_weight is None else ctc_weight)
@@ -461,6 +503,11 @@ class Decode(object):
         if self.lm is None and lm_weight is not None and lam > 0.0:
             raise ValueError("decode_two_pass: lm_weight needs the language model (Decode(..., lm=...))")
         fuse = self.lm is not None and (lam > 0.0 or self.lm_length_bonus != 0.0)
+        bw = float(self.bias_weight if bias_weight is None else bias_weight)
+        if not bw >= 0.0 or not math.isfinite(bw):
+            raise ValueError("decode_two_pass: bias_weight must be a finite number >= 0, got %r" % bw)
+        if self.bias is None and bias_weight is not None and bw > 0.0:
+            raise ValueError("decode_two_pass: bias_weight needs the context bias (Decode(..., bias=...))")
         beam, K, N = self._ctc_widths("decode_two_pass", beam, n_best)
         if self.max_steps < 2:
             raise ValueError("decode_two_pass: max_steps must allow a label and EOS")
@@ -479,6 +526,10 @@ class Decode(object):
                 extra = self.lm_length_bonus * lens1
                 if lam > 0.0:
                     extra = extra + lam * self.lm_score(nbest).double().cpu()
+            if self.bias is not None and bw > 0.0:
+                boost = bw * self.bias_score(nbest).double().cpu()
+                boost = torch.where(torch.isfinite(boost), boost, torch.zeros_like(boost))     # (a missing list: att is -inf already)
+                extra = boost if extra is None else extra + boost
         all_hyp, scores = ctc_beam.combine(hyps, ctc_scores, att, w, N, Constants.EOS, extra=extra)
         return all_hyp, list(scores.to(self.device).unbind(0))
 
@@ -547,7 +598,8 @@ class Decode(object):
         arena = arena_of(model)
         with arena.scope():
             st = self._init_state(src_batch, beam, arena,
-                                  ctc=(self.ctc_pre_beam, self.ctc_weight) if self.ctc_pre_beam is not None else None, lm=self._lm_on)
+                                  ctc=(self.ctc_pre_beam, self.ctc_weight) if self.ctc_pre_beam is not None else None, lm=self._lm_on,
+                                  bias=self.bias if self._bias_on else None)
             S = self.max_steps
 
             def one_step():
