@@ -55,7 +55,9 @@ enum {
   ST_EPI_BF16_RELU = 1,  /* D(bf16) = relu(acc + bias)      SubLayers.py:25          */
   ST_EPI_F32 = 2,        /* D(f32)  = acc (+ bias)          Models.py:151 (logits)   */
   ST_EPI_BF16_MASK = 3,  /* D(bf16) = acc * (aux > 0)       ReLU backward            */
-  ST_EPI_BF16_ADD = 4,   /* D(bf16) = acc + aux             residual-gradient add    */
+  ST_EPI_BF16_ADD = 4,   /* D(bf16) = bf16(bf16(acc + bias) + aux): residual-gradient add.  TWO roundings - the GEMM result
+                            is rounded to bf16 before the addend joins it (the fused st_gemm_lnbwd rounds acc + aux once
+                            and differs by that rounding).  aux may be D itself (in place: same pointer, same ld) */
   ST_EPI_F32_ATOMIC = 5, /* D(f32) += acc (atomic, split-K)                          */
   ST_EPI_F32_ATOMIC_T = 6, /* D^T(f32)[j][i] += acc: weight gradients, coalesced atomics */
   ST_EPI_BF16_DELTA = 7  /* D(bf16) = acc, and delta[h][i] = sum_{j in head h} D(i,j) * (aux(i,j) + aux2(i,j)); aux2

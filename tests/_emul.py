@@ -68,7 +68,9 @@ def keep_qk(d, bh, nq, nk):
 
 
 def gemm(X, Y, out, bias=None, aux=None, epi=nv.EPI_BF16, x_cmajor=False, y_cmajor=False, splits=1, m=None, n=None,
-         kc=None, drop=None, delta=None, head_dim=0, stack=None, aux2=None, dtype=F32):
+         kc=None, drop=None, delta=None, head_dim=0, stack=None, aux2=None, dtype=F32, add_once=False):
+    """add_once (emulation only, no such argument in st_amd.native.gemm): EPI_BF16_ADD as the fused st_gemm_lnbwd forms it - acc + aux
+    rounded ONCE; st_gemm itself rounds the GEMM result to bf16 before the addend joins it (include/st_hip.h)."""
     if stack is not None:       # Y / bias: the first of `blocks` equally spaced blocks (st_gemm_stacked)
         blocks, y_stride, b_stride = stack
         Y = torch.as_strided(Y, (blocks, Y.shape[0], Y.shape[1]), (y_stride, Y.stride(0), 1)).reshape(-1, Y.shape[1])
@@ -93,8 +95,8 @@ def gemm(X, Y, out, bias=None, aux=None, epi=nv.EPI_BF16, x_cmajor=False, y_cmaj
             acc = acc * keep_rc(drop, torch.arange(M), torch.arange(N), N) * drop.scale
     elif epi == nv.EPI_BF16_MASK:
         acc = acc * (aux[:M, :N].to(dtype) > 0) * (drop.scale if _on(drop) else 1.0)
-    elif epi == nv.EPI_BF16_ADD:
-        acc = acc + aux[:M, :N].to(dtype)
+    elif epi == nv.EPI_BF16_ADD:      # include/st_hip.h: the GEMM result is rounded to bf16 BEFORE the addend joins it, the sum again
+        acc = (acc if add_once else acc.to(BF16).to(dtype)) + aux[:M, :N].to(dtype)
     if epi == nv.EPI_F32_ATOMIC:
         out[:M, :N] += acc
     elif epi == nv.EPI_F32_ATOMIC_T:
@@ -312,7 +314,7 @@ def row_chain_bwd(chain, M, head=None, ds_in=None, ffn=None, tail=None, dtype=F3
 
 def gemm_lnbwd(dY, W, aux, xhat, rstd, gamma, dx, dgamma=None, dbeta=None, dbias=None, drop=None, dtype=F32, dbias_rounded=False):
     dy = torch.zeros(dY.shape[0], W.shape[1], dtype=BF16)
-    gemm(dY, W, dy, aux=aux, epi=nv.EPI_BF16_ADD if aux is not None else nv.EPI_BF16, y_cmajor=True, dtype=dtype)
+    gemm(dY, W, dy, aux=aux, epi=nv.EPI_BF16_ADD if aux is not None else nv.EPI_BF16, y_cmajor=True, dtype=dtype, add_once=True)
     return ln_bwd(dy, xhat[:dY.shape[0]], rstd, gamma, dx, dgamma, dbeta, dbias, drop=drop, dtype=dtype, dbias_rounded=dbias_rounded)
 
 

@@ -316,10 +316,11 @@ def serial_ln_bwd(dy, xhat, rstd, gamma, dx, dgamma=None, dbeta=None, dbias=None
     return dx
 
 
-def chunked_gemm(X, Y, out, aux=None, epi=None, y_cmajor=False, delta=None, head_dim=0, aux2=None, dtype=F32):
+def chunked_gemm(X, Y, out, aux=None, epi=None, y_cmajor=False, delta=None, head_dim=0, aux2=None, dtype=F32, add_once=True):
     """tests._emul.gemm for the data-gradient products of this family (Y [Kc, N] as stored), the contraction accumulated serially
     over chunks of 32 - one MFMA step - and delta's products one by one: another summation order, hence other bf16 values of dy
-    that land on the far side of a rounding boundary."""
+    that land on the far side of a rounding boundary.  EPI_BF16_ADD only in the fused kernels' form (acc + aux rounded once)."""
+    assert add_once
     from st_amd import native as nv
     epi = nv.EPI_BF16 if epi is None else epi
     assert y_cmajor and epi in (nv.EPI_BF16, nv.EPI_BF16_ADD, nv.EPI_BF16_DELTA)
